@@ -2,7 +2,7 @@
 """Benchmark of the hot path: one VI_Model1 training step (image-row gather -> forward -> ELBO -> backward ->
 [gradient all-reduce] -> clip + Adam) on synthetic batches.
 
-    python bench.py --gpus N --steps K --warmup W [--config 2|5|script]
+    python bench.py --gpus N --steps K --warmup W [--config 2|5|script] [--dump-outputs DIR] [--full]
 
 --config 2 (default; the configuration BASELINE.json's metric is quoted on): batch 256 per GPU, src/tgt length 20, 30k
 vocabularies, 1-layer biLSTM 512, z 256, emb 500 (reference default), 2048-d image features, bf16 compute / fp32
@@ -15,8 +15,21 @@ bench.py --gpus N ...`: RANK / WORLD_SIZE are in the environment) or a plain `py
 parent process then only spawns `torch.distributed.run` as a child BEFORE touching any GPU, relays rank 0's JSON line and
 exits with the child's code.
 
-Prints ONE JSON line on rank 0 (metric = triplets/sec, whole job).  `roofline` is for the dominant kernel (timed live
-with events on the launch stream); `cpu_baseline` is the CPU oracle timed on the host cores (rank 0, N = 1 only).
+Prints ONE JSON line on rank 0 (metric = triplets/sec, whole job; `ms_per_step` = the timed region's wall clock over its K steps).
+
+A plain run does what that figure needs and nothing else: set-up, warm-up, ONE timed region of K steps, the line.  `--full` adds what the
+benchmark measures beside it: `roofline` for the dominant kernel (timed live with events on the launch stream), the stream-overlap
+self-check, the timed region repeated (`--repeats`), the `parity` gate against the CPU oracle, `cpu_baseline` (the CPU oracle timed on the
+host cores; rank 0, N = 1 only) and the per-segment collective timing of a multi-GPU line.
+
+`--dump-outputs DIR` writes what the timed region's last step computes as DIR/<name>.npy (dump_outputs): the step's statistics, the
+per-token NLL, every gradient and every parameter behind the update.  Batches, image table, initial parameters and dropout masks are
+seeded.  The arrays come from the timed engine itself, put back into the seeded state behind the timed regions and taken through the
+region's last step once more (dump_last_step in main: a training loop's own state carries its float atomics' noise, enlarged by every
+update): two runs with the same arguments write the same arrays up to a bf16 rounding step.
+
+`--repeats`, `--no-cpu-baseline`, `--no-parity` and `--no-overlap-probe` shape what `--full` adds; without `--full` they do nothing (a note
+on stderr says so).
 """
 import argparse
 import json
@@ -427,6 +440,41 @@ def through_trainer(a, dev, rank, world):
         emit(out)
 
 
+DUMP_SAMPLE = 131072          # elements written of a parameter tensor that has more
+STAT_KEYS = ("nmt", "td_kl_before", "td_kl_after", "img_feats_loss", "img_feats_cos", "elbo", "n_words", "n_correct")
+
+
+def sample_indices(names_numel, cap=DUMP_SAMPLE, seed=20):
+    """{name: int64 flat indices} for the tensors with more than `cap` elements: `cap` indices each, drawn from one generator seeded with
+    `seed` walking the names in sorted order -- the same elements in every run, whatever order the caller lists the tensors in"""
+    g = torch.Generator().manual_seed(seed)
+    return {n: torch.randint(0, k, (cap,), generator=g) for n, k in sorted(names_numel.items()) if k > cap}
+
+
+def dump_outputs(path, eng, ws, batch_global):
+    """what the step that has just run left with its caller, one float32 / float64 .npy per array under `path`: stats (float64, in
+    STAT_KEYS' order: Engine.read_stats), tok_nll (float32 [T', B]: the per-token NLL of the step's batch), grad.<name> for every
+    gradient of the step and param.<name> for every parameter behind its update (float32; a tensor of more than DUMP_SAMPLE elements as
+    a fixed seeded sample of its flattened elements: sample_indices).  Synchronises (Engine.state_dict flushes a held-back update and the
+    lazily updated embedding rows, as for every reader of the parameters).  -> bytes written"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    st = eng.read_stats(ws, batch_global=batch_global)
+    arrays = {"stats": np.array([float(st[k]) for k in STAT_KEYS], dtype=np.float64),
+              "tok_nll": ws.tok_nll.detach().float().cpu().view(ws.Tp, ws.B).numpy()}
+    sd = eng.state_dict()
+    idx = sample_indices({n: v.numel() for n, v in sd.items()})
+    for kind, tensors in (("param.", sd), ("grad.", eng.grads)):
+        for n, v in tensors.items():
+            flat = v.reshape(-1)
+            arrays[kind + n] = (flat[idx[n].to(flat.device)] if n in idx else v).float().cpu().numpy()
+    total = sum(x.nbytes for x in arrays.values())
+    assert total <= 64 * 2 ** 20, "dump of %d bytes" % total
+    for n, x in arrays.items():
+        np.save(os.path.join(path, n + ".npy"), x)
+    return total
+
+
 _REAL_STDOUT = None
 
 
@@ -489,10 +537,16 @@ def main():
     ap.add_argument("--batch", type=int, default=256, help="per-GPU batch (weak scaling)")
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--dropout", type=float, default=0.5)
-    ap.add_argument("--repeats", type=int, default=3, help="timed regions run back to back in the same process; the FIRST is the metric, the "
-                    "others are reported beside it (`repeats_ms`) to show whether it was typical for the box")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the parity gate (one cfg-1-shaped step against the CPU oracle)")
+    ap.add_argument("--full", action="store_true", help="everything the benchmark measures beside its headline figure: the dominant kernel's "
+                    "roofline, the stream-overlap self-check, repeated timed regions, the parity gate, the CPU baseline, per-segment collective "
+                    "timing (N > 1).  Off: set-up, warm-up, one timed region, the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="behind the timed regions, take the timed engine through the region's last step once more "
+                    "from the seeded state and write what it computes (statistics, per-token NLL, gradients, updated parameters; large "
+                    "tensors as a fixed seeded sample) as DIR/<name>.npy")
+    ap.add_argument("--repeats", type=int, default=None, help="with --full: timed regions run back to back in the same process; the FIRST is the "
+                    "metric, the others are reported beside it (`repeats_ms`) to show whether it was typical for the box")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the parity gate (one cfg-1-shaped step against the CPU oracle)")
     ap.add_argument("--no-side-stream", action="store_true", help="profiling aid: issue the whole step on one stream")
     ap.add_argument("--no-overlap-probe", action="store_true", help="profiling aid (tools/prof.sh, tools/pmc.sh): leave out the stream-overlap "
                     "self-check, whose 13 extra steps -- 6 of them on ONE stream -- would be averaged into a kernel profile of the run")
@@ -506,6 +560,11 @@ def main():
                     "the engine-level step")
     ap.add_argument("--selftest-launch", action="store_true", help="CPU check of the N-rank launch path: gloo ranks, one all-reduce, no GPU")
     a = ap.parse_args()
+    if not a.full and (a.repeats is not None or a.no_cpu_baseline or a.no_parity or a.no_overlap_probe):
+        sys.stderr.write("bench.py: --repeats / --no-cpu-baseline / --no-parity / --no-overlap-probe only shape a --full run; this is a plain run "
+                         "(one timed region, none of those blocks)\n")
+    if a.repeats is None:
+        a.repeats = 3
 
     if a.gpus > 1 and "RANK" not in os.environ:
         launch_ranks(a)           # does not return
@@ -556,6 +615,8 @@ def main():
             dist.init_process_group(backend)
 
     if a.through_trainer:
+        if a.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs writes the engine-level step's outputs; it does not go with --through-trainer")
         return through_trainer(a, dev, rank, world)
     from variational_mmt_amd.engine import Dims, Engine
     cf = CONFIGS[a.config]
@@ -601,6 +662,33 @@ def main():
         eng.optim_step(lr=0.002, max_grad_norm=5.0)
         return ws
 
+    # `--dump-outputs`: the state every run begins in (parameters; the eps / dropout counter, which GradSync has offset by the rank)
+    seeded = (eng.state_dict(), eng.rng_counter) if a.dump_outputs else None
+
+    def dump_last_step(path):
+        """`--dump-outputs`, behind every timed region: the official region's last step once more on the timed path itself -- this engine
+        with its launch plans and workspaces as the regions left them, the same step(), collectives and normalisation -- from the state
+        the run began in (seeded parameters, a new Adam as onmt.Optim.set_parameters makes one, the eps / dropout counter), and what it
+        left with its caller written (dump_outputs).
+        Why from the seeded state, and why ONE step: a step's gradients carry float-atomic noise from run to run, and Adam's first
+        updates (m / sqrt(v) = the gradient's sign) and every bf16 rounding enlarge it.  Two runs of ONE build, config 2
+        (profiles/dump_outputs_run_to_run.txt): behind one step from the seed every array within 5e-4 of its largest value and the
+        per-token NLL bit-equal; behind three steps already 6e-3 nats in a token's NLL and 10 % of the largest value in the smallest
+        gradients; behind the warm-up + 50 updates of a run 0.06 nats and 4 % (relative L2) in the q(z|x) layers' parameters -- nothing
+        another build's arrays could be held against.  tests/test_gpu_bench_cli.py holds two runs to one bf16 step."""
+        eng.wait_background()
+        torch.cuda.synchronize()
+        eng.load_state_dict(seeded[0])
+        eng.flat_m.zero_()
+        eng.flat_v.zero_()
+        eng.flat_g.zero_()               # (the tables' gradient rows of earlier batches: stale under the lazy update, and written with the rest)
+        eng.step_count = 0
+        eng.rng_counter = seeded[1]
+        ws_ = step(n_warm + a.steps - 1)
+        eng.wait_background()            # (the held-back half of the update goes out here)
+        torch.cuda.synchronize()
+        return dump_outputs(path, eng, ws_, B)
+
     # ---- dominant-kernel timing hooks: events on the launch stream around the generator kernels -----------------
     ws0 = eng.workspace(B, S, Tp)        # (ragged lengths: the hooks sit on the full-length bucket only; other buckets run unhooked)
     dom = {"gen_fwd": [], "gen_bwd": []}
@@ -625,7 +713,7 @@ def main():
         timed_fn.__name__ = name
         plan[index] = (timed_fn, args, name, keep, sid)
 
-    for j, (fn, args, name, keep, sid) in enumerate(ws0.plan_loss_train):
+    for j, (fn, args, name, keep, sid) in enumerate(ws0.plan_loss_train if a.full else ()):
         if name in ("vmmt_gen_fwd_dO", "vmmt_gen_loss_fwd"):
             wrap(ws0.plan_loss_train, j, "gen_fwd")
 
@@ -635,7 +723,7 @@ def main():
     state0 = gpu_state()
     step(0)                            # builds the launch plans (the backward plan exists behind the first step)
     # backward plan exists now: hook the gen_loss_bwd entry
-    for j, (fn, args, name, keep, sid) in enumerate(ws0.plan_bwd):
+    for j, (fn, args, name, keep, sid) in enumerate(ws0.plan_bwd if a.full else ()):
         if name in ("vmmt_gen_loss_bwd", "vmmt_gen_loss_bwd_db"):
             wrap(ws0.plan_bwd, j, "gen_bwd")
 
@@ -685,7 +773,7 @@ def main():
     gc.collect()
     gc.freeze()
     overlap = None
-    if world == 1 and not a.no_side_stream and not a.no_overlap_probe:
+    if a.full and world == 1 and not a.no_side_stream and not a.no_overlap_probe:
         def timed_steps(n, first):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             torch.cuda.synchronize()
@@ -708,9 +796,9 @@ def main():
     for i in range(n_warm):
         step(i)
     regions = []
-    n_rep = max(1, a.repeats)
+    n_rep = max(1, a.repeats) if a.full else 1
     for r_ in range(n_rep):            # the FIRST region is the official one; the others show whether it was typical for the box
-        regions.append(timed_region(n_warm + r_ * a.steps, hooks=(r_ == 0)) + (gpu_state(),))
+        regions.append(timed_region(n_warm + r_ * a.steps, hooks=(a.full and r_ == 0)) + (gpu_state(),))
     dt, ws, dev_ms, host_ms, enq_ms, sched = regions[0][:6]
     if dist is not None:
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
@@ -720,19 +808,23 @@ def main():
     eng.check_async_errors()           # settles a persistent-kernel hand-off that timed out (fallback + warning; reported below)
     dp_block = None
     if sync.active():
-        # the multi-GPU line must be auditable: which backend ran, which form of each collective, how many ranks it saw, and what every
-        # segment's collective cost -- timed over a few EXTRA steps behind the timed region (events on the step would perturb it)
-        sync.timing, sync.exposed = [], []
-        for i in range(min(10, max(3, a.steps))):
-            sync.step_event = torch.cuda.Event(enable_timing=True)
-            sync.step_event.record()
-            step(a.warmup + a.steps + i)
-        segs, exposed = sync.timing_report()
-        sync.timing = None
+        # the multi-GPU line must be auditable: which backend ran, which form of each collective, how many ranks it saw, and (--full) what
+        # every segment's collective cost -- timed over a few EXTRA steps behind the timed region (events on the step would perturb it)
         dp_block = {"backend": sync.backend, "world_seen": dist.get_world_size() if dist is not None else sync.world, "sharded_optimizer": bool(sync.sharded),
                     "native_collectives": sync.native_collectives(), "branches": ["%s: %s (%s)" % b_ for b_ in sync.branch_log],
-                    "segments": segs, "exposed_ms": round(sum(exposed.values()), 4), "exposed_by_wait_ms": exposed,
                     "persistent_lstm": bool(eng.persistent_lstm)}
+        if a.full:
+            sync.timing, sync.exposed = [], []
+            for i in range(min(10, max(3, a.steps))):
+                sync.step_event = torch.cuda.Event(enable_timing=True)
+                sync.step_event.record()
+                step(a.warmup + a.steps + i)
+            segs, exposed = sync.timing_report()
+            sync.timing = None
+            dp_block.update({"segments": segs, "exposed_ms": round(sum(exposed.values()), 4), "exposed_by_wait_ms": exposed})
+    dumped = None
+    if a.dump_outputs:
+        dumped = dump_last_step(a.dump_outputs if world == 1 else os.path.join(a.dump_outputs, "rank%d" % rank))
 
     if rank == 0:
         fl = flops_per_triplet(d, S, Tp)
@@ -741,38 +833,50 @@ def main():
         step_sum, slow_steps, step_med = step_summary(dev_ms, host_ms)
         reps = [r_[0] / a.steps * 1e3 for r_ in regions]
         diagnosis = diagnose(ms, a.steps, step_med, slow_steps, enq_ms, sched, reps, overlap)
-        # dominant kernel = the fused vocabulary projection (+log-softmax+NLL) GEMM passes: 2*M*V*H FLOP per launch
-        M = Tp * B
-        fused = bool(getattr(ws0, "gen_fused", False))
-        # per launch: one [M x V x H] product in the G^T path (generator.hip), two in the fused sweep (generator_fused.hip:
-        # logits + dO; its time includes the combine kernel behind it)
-        gen_flop = (4.0 if fused else 2.0) * M * d.vt * d.hid
-        # per step: the backward pass may walk the vocabulary in several launches (Engine.gen_chunks); their times add up
-        t_f = sum(s.elapsed_time(e_) for s, e_ in dom["gen_fwd"]) / max(1, a.steps)      # ms (fwd incl. combine)
-        t_b = sum(s.elapsed_time(e_) for s, e_ in dom["gen_bwd"]) / max(1, a.steps)
-        t_dom = max(t_f, t_b)
-        ach = gen_flop / (t_dom * 1e-3) / 1e12 if t_dom > 0 else 0.0
-        if fused and dom.get("gen_fwd_tokens"):      # per launch as issued: 4 H V x the launch's own token count over its own time
-            tsum = sum(s.elapsed_time(e_) for s, e_ in dom["gen_fwd"])
-            ach = 4.0 * sum(dom["gen_fwd_tokens"]) * d.vt * d.hid / (tsum * 1e-3) / 1e12 if tsum > 0 else 0.0
-        # HBM bytes per launch of the dominant kernel from the committed PMC passes (profiles/traffic.json).  The entry names the source
-        # text it was measured on -- the kernel's own region of its .hip file (tools/traffic_key.py), so that an edit elsewhere in the
-        # file does not void it, and tests/test_traffic_json.py fails while the region and the entry disagree
-        traffic, traffic_note = None, None
-        try:
-            tj = json.load(open(os.path.join(ROOT, "profiles", "traffic.json")))["config%s" % a.config]
-            if B == 256 and a.dtype == "bf16" and not a.conditional and a.lengths == "fixed":
-                sys.path.insert(0, os.path.join(ROOT, "tools"))
-                import traffic_key
-                traffic = tj["read_bytes"] + tj["write_bytes"]
-                sha = traffic_key.key_hash(tj["kernel_region"])
-                if sha != tj["kernel_region_sha16"]:
-                    traffic_note = ("measured on an EARLIER revision of %s's source region (%s, now %s): re-run tools/pmc.sh" %
-                                    (tj["kernel_region"], tj["kernel_region_sha16"], sha))
-            else:
-                traffic_note = "the PMC pass was taken at batch 256, bf16, fixed lengths, fixed prior: no figure for this variation"
-        except Exception as ex:
-            traffic_note = "no PMC figure for this configuration (%s)" % type(ex).__name__
+        roofline = None
+        if a.full:
+            # dominant kernel = the fused vocabulary projection (+log-softmax+NLL) GEMM passes: 2*M*V*H FLOP per launch
+            M = Tp * B
+            fused = bool(getattr(ws0, "gen_fused", False))
+            # per launch: one [M x V x H] product in the G^T path (generator.hip), two in the fused sweep (generator_fused.hip:
+            # logits + dO; its time includes the combine kernel behind it)
+            gen_flop = (4.0 if fused else 2.0) * M * d.vt * d.hid
+            # per step: the backward pass may walk the vocabulary in several launches (Engine.gen_chunks); their times add up
+            t_f = sum(s.elapsed_time(e_) for s, e_ in dom["gen_fwd"]) / max(1, a.steps)      # ms (fwd incl. combine)
+            t_b = sum(s.elapsed_time(e_) for s, e_ in dom["gen_bwd"]) / max(1, a.steps)
+            t_dom = max(t_f, t_b)
+            ach = gen_flop / (t_dom * 1e-3) / 1e12 if t_dom > 0 else 0.0
+            if fused and dom.get("gen_fwd_tokens"):      # per launch as issued: 4 H V x the launch's own token count over its own time
+                tsum = sum(s.elapsed_time(e_) for s, e_ in dom["gen_fwd"])
+                ach = 4.0 * sum(dom["gen_fwd_tokens"]) * d.vt * d.hid / (tsum * 1e-3) / 1e12 if tsum > 0 else 0.0
+            # HBM bytes per launch of the dominant kernel from the committed PMC passes (profiles/traffic.json).  The entry names the source
+            # text it was measured on -- the kernel's own region of its .hip file (tools/traffic_key.py), so that an edit elsewhere in the
+            # file does not void it, and tests/test_traffic_json.py fails while the region and the entry disagree
+            traffic, traffic_note = None, None
+            try:
+                tj = json.load(open(os.path.join(ROOT, "profiles", "traffic.json")))["config%s" % a.config]
+                if B == 256 and a.dtype == "bf16" and not a.conditional and a.lengths == "fixed":
+                    sys.path.insert(0, os.path.join(ROOT, "tools"))
+                    import traffic_key
+                    traffic = tj["read_bytes"] + tj["write_bytes"]
+                    sha = traffic_key.key_hash(tj["kernel_region"])
+                    if sha != tj["kernel_region_sha16"]:
+                        traffic_note = ("measured on an EARLIER revision of %s's source region (%s, now %s): re-run tools/pmc.sh" %
+                                        (tj["kernel_region"], tj["kernel_region_sha16"], sha))
+                else:
+                    traffic_note = "the PMC pass was taken at batch 256, bf16, fixed lengths, fixed prior: no figure for this variation"
+            except Exception as ex:
+                traffic_note = "no PMC figure for this configuration (%s)" % type(ex).__name__
+            roofline = {"bound": "mfma", "kernel": (("gen2w_kernel" if d.hid > 512 else "gen2p_kernel" if d.hid > 256 else "gen2_kernel") + " (fused vocabulary sweep: logits + softmax statistics + dO, softmax weights stored for the dWg GEMM)" if fused else
+                                   "gen_kernel (vocab projection + log-softmax/NLL pass, slower of fwd/bwd)"),
+                        "achieved": round(ach, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                        "frac": round(ach / PEAK_BF16_TFLOPS, 4), "traffic": traffic, "traffic_note": traffic_note,
+                        # what the sweep must read at least -- Wg once, O once (bf16) -- against which `traffic` is to be judged: the rest of
+                        # it is the softmax weights P [tokens][V] (bf16) + per-slice partials written for the dWg product, which reads P back
+                        "traffic_operands": (d.vt * d.hid + M * d.hid) * 2 if fused else None,
+                        "traffic_P_written": (M * d.vt * 2) if fused else None,
+                        "ms_fwd": round(t_f, 4), "ms_bwd": round(t_b, 4),
+                        "step_tflops": round(3 * fl["total"] * Bg / (dt / a.steps) / 1e12, 2)}
         out = {
             "metric": "triplets/sec", "value": round(value, 1), "unit": "triplets/sec", "n_gpus": world,
             "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True,
@@ -780,16 +884,6 @@ def main():
             "config": {"workload": (cf["name"] % B) + ", dropout %.1f, Adam%s%s" % (a.dropout, ", --conditional prior" if a.conditional else "",
                                                                                     ", lengths U[10,20]" if a.lengths == "ragged" else ""),
                        "global_batch": Bg, "parallelism": "dp%d" % world, "image_rows": n_img},
-            "roofline": {"bound": "mfma", "kernel": (("gen2w_kernel" if d.hid > 512 else "gen2p_kernel" if d.hid > 256 else "gen2_kernel") + " (fused vocabulary sweep: logits + softmax statistics + dO, softmax weights stored for the dWg GEMM)" if fused else
-                                    "gen_kernel (vocab projection + log-softmax/NLL pass, slower of fwd/bwd)"),
-                         "achieved": round(ach, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(ach / PEAK_BF16_TFLOPS, 4), "traffic": traffic, "traffic_note": traffic_note,
-                         # what the sweep must read at least -- Wg once, O once (bf16) -- against which `traffic` is to be judged: the rest of
-                         # it is the softmax weights P [tokens][V] (bf16) + per-slice partials written for the dWg product, which reads P back
-                         "traffic_operands": (d.vt * d.hid + M * d.hid) * 2 if fused else None,
-                         "traffic_P_written": (M * d.vt * 2) if fused else None,
-                         "ms_fwd": round(t_f, 4), "ms_bwd": round(t_b, 4),
-                         "step_tflops": round(3 * fl["total"] * Bg / (dt / a.steps) / 1e12, 2)},
             # what explains the value: device time of every step of the official region (events on the main stream), the host's time to
             # enqueue it, the same region repeated, the steps that took > 1.5 x the median, the box's clocks before / after
             "step_ms": step_sum, "value_median": round(Bg / (step_med * 1e-3), 1),
@@ -809,14 +903,18 @@ def main():
             # head is through (two or more layers, one rank) or issued at once; the last one is flushed inside the timed region
             "held_back_update": bool(eng.hold_back and eng.bg_after_head and not a.conditional and not sync.active()),
         }
+        if roofline is not None:
+            out["roofline"] = roofline
+        if dumped is not None:
+            out["outputs_dumped"] = {"dir": a.dump_outputs, "bytes": dumped}
         if dp_block is not None:
             out["dp"] = dp_block
-        if world == 1 and not a.no_parity:
+        if a.full and world == 1 and not a.no_parity:
             try:
                 out["parity"] = parity_gate(dev, a.dtype, a.dropout)
             except Exception as ex:          # the gate failing to RUN must not take the measured line with it; it is reported as such
                 out["parity"] = {"error": "%s: %s" % (type(ex).__name__, str(ex)[:300])}
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         emit(out)
     if dist is not None:

@@ -9,7 +9,7 @@ if [ "$what" = driver ] || [ "$what" = all ]; then
   python bench.py --gpus 1 --steps 20 --warmup 5 > $out/driver_args.json 2> $out/driver_args.err || exit 1
 fi
 if [ "$what" = smi ] || [ "$what" = all ]; then
-  short="--gpus 1 --steps 20 --warmup 5 --repeats 12 --no-cpu-baseline --no-parity"
+  short="--full --gpus 1 --steps 20 --warmup 5 --repeats 12 --no-cpu-baseline --no-parity"
   python bench.py $short > $out/quiet.json 2> $out/quiet.err || exit 1
   for tool in "rocm-smi -a --json" "amd-smi metric --json" "rocm-smi --showuse --showpower --showclocks --json"; do
     name=$(echo "$tool" | tr -c 'a-z\n' '_' | cut -c1-24)
@@ -22,7 +22,7 @@ if [ "$what" = smi ] || [ "$what" = all ]; then
 fi
 if [ "$what" = hog ] || [ "$what" = all ]; then
   # a busy host: 3 spinning processes per CPU this box gives us, next to the bench's one enqueueing thread
-  short="--gpus 1 --steps 20 --warmup 5 --repeats 6 --no-cpu-baseline --no-parity"
+  short="--full --gpus 1 --steps 20 --warmup 5 --repeats 6 --no-cpu-baseline --no-parity"
   n=${HOGS:-48}; pids=""      # (nproc shows the whole host: 256; the box gives one GPU's lease a share of 16)
   for i in $(seq $n); do ( exec timeout 120 sh -c 'while :; do :; done' ) & pids="$pids $!"; done
   python bench.py $short > $out/with_host_hogs_x$n.json 2> $out/with_host_hogs.err; rc=$?

@@ -1,4 +1,4 @@
-NP="--no-cpu-baseline --no-parity"
+NP="--full --no-cpu-baseline --no-parity"
 run() { echo -n "$*   "; "${ENVV[@]}" python bench.py $NP "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], 'triplets/s', d['ms_per_step'], 'ms/step  elbo/sentence', d.get('elbo_per_sentence'), ' seq_fallbacks', d.get('seq_fallbacks'), 'steps_skipped', d.get('steps_skipped'))"; }
 ENVV=(env X=1)
 run --steps 10000 --warmup 10
