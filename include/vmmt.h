@@ -229,6 +229,26 @@ int vmmt_attn_bwd(int dtype, const void* dcat, int64_t lddc, const float* probs,
 int vmmt_attn_bwd_long(int dtype, const void* dcat, int64_t lddc, const float* probs, const void* q, int64_t ldq,
                        const void* ctx, int64_t ldc, const int64_t* lens, void* dq, int64_t lddq, void* dctx, int64_t lddx,
                        int Tp, int B, int S, int H, float* dots, void* stream);
+/* ---- attention ("mlp", Bahdanau): score[t][s] = v . tanh(W_q r_t + b_q + W_c Hs_s) -------------------------------
+ * parameters: onmt/modules/GlobalAttention.py:70-78; score :114-127; mask, softmax, context :171-184 (as "general").
+ *   wq   T [Tp*B][ldwq]  rows t*B+b: W_q r (linear_query without its bias, by vmmt_gemm) ; bq f32 [H]: its bias
+ *   uh   T [S*B][lduh]   rows s*B+b: W_c Hs (linear_context, by vmmt_gemm) ; v f32 [H]
+ *   ctx, lens, cat, probs: as vmmt_attn_fwd (context into columns [0,H) of the concat buffer, probs f32 [Tp][B][S], 0 at pads)
+ * limits: S <= 256, H <= 1024 (VMMT_EINVAL beyond); S <= 64 in bf16: per-sentence LDS kernel, otherwise one wave per query. */
+int vmmt_attn_mlp_fwd(int dtype, const void* wq, int64_t ldwq, const float* bq, const void* uh, int64_t lduh, const float* v,
+                      const void* ctx, int64_t ldc, const int64_t* lens, void* cat, int64_t ldcat, float* probs, int Tp, int B,
+                      int S, int H, void* stream);
+/* backward (GlobalAttention.py:114-127,179-184 differentiated; tanh recomputed, never stored): dcat columns [0,H) hold dL/dc.
+ *   dwq T [Tp*B][lddwq], duh T [S*B][ldduh] (zero at pads), dctx T [S*B][lddx]: the DIRECT path sum_t p[t][s] dc_t only (zero at
+ *   pads, every valid row overwritten; the path through uh is the caller's GEMM duh W_c)
+ *   dv_part f32 [vmmt_attn_mlp_dv_parts(B, H)][H]: per-workgroup partial sums of dv, every entry written; the caller folds the rows
+ *   with vmmt_colsum.  No floating-point atomics: the result is bit-reproducible.
+ * limits: S <= 64 and T' <= 64, H <= 1024 (VMMT_EINVAL beyond). */
+int vmmt_attn_mlp_dv_parts(int B, int H);
+int vmmt_attn_mlp_bwd(int dtype, const void* dcat, int64_t lddc, const float* probs, const void* wq, int64_t ldwq, const float* bq,
+                      const void* uh, int64_t lduh, const float* v, const void* ctx, int64_t ldc, const int64_t* lens, void* dwq,
+                      int64_t lddwq, void* duh, int64_t ldduh, void* dctx, int64_t lddx, float* dv_part, int Tp, int B, int S,
+                      int H, void* stream);
 /* hbar[b] = mean_{s<len_b} ctx[s][b]  (GlobalInferenceNetwork.encode_seq, modules/NormalVariationalEncoder.py:65-84) */
 int vmmt_masked_mean(int dtype, const void* ctx, int64_t ldc, const int64_t* lens, void* out, int64_t ldo, int B, int S,
                      int H, void* stream);

@@ -40,6 +40,13 @@ class _Stepper(object):
         self.Q, self.AH = nb(R, H), nb(R, H)
         self.probs = torch.zeros(R * S, dtype=f32, device=dev)
         self.ctx, self.ctx_ld, self.src_len, self.zx, self.zx_ld = ctx, ctx_ld, src_len, zx, zx_ld
+        self.UH = nb(S * R, H) if d.attn == "mlp" else None      # W_c Hs of the mlp attention: per batch, not per position
+
+    def prepare(self):
+        """what depends on the batch's source memory alone, once the decoder state is built: UH = Hs W_c^T (GlobalAttention.py:122-123)"""
+        if self.UH is not None:
+            wc = self.eng.sh["wc"]
+            self.gemm(L.GEMM_NT, self.ctx, self.ctx_ld, wc.p(), wc.ld, self.UH.p(), self.UH.ld, self.S * self.R, self.eng.d.hid, self.eng.d.hid)
 
     def gemm(self, layout, A, lda, Bp, ldb, Cp, ldc, M, N, K, **kw):
         e = self.eng
@@ -86,8 +93,18 @@ class _Stepper(object):
             x, xoff, xcols = ho[0], ho[1], H
         cat = self.cat[1]
         wa, wo = e.sh["wa"], e.sh["wo"]
-        self.gemm(L.GEMM_NT, cat.p(0, Hp), cat.ld, wa.p(), wa.ld, self.Q.p(), self.Q.ld, R, H, H)
-        L.check(lib.vmmt_attn_fwd(dt, self.Q.p(), self.Q.ld, self.ctx, self.ctx_ld, self.src_len.data_ptr(), cat.p(), cat.ld,
+        if d.attn == "mlp":
+            self.gemm(L.GEMM_NT, cat.p(0, Hp), cat.ld, wa.p(), wa.ld, self.Q.p(), self.Q.ld, R, H, H)
+            L.check(lib.vmmt_attn_mlp_fwd(dt, self.Q.p(), self.Q.ld, e.sh["attn_bq"].p(), self.UH.p(), self.UH.ld,
+                                          e.sh["attn_v"].p(), self.ctx, self.ctx_ld, self.src_len.data_ptr(), cat.p(), cat.ld,
+                                          self.probs.data_ptr(), 1, R, self.S, Hp, st), "vmmt_attn_mlp_fwd")
+            self.gemm(L.GEMM_NT, cat.p(), cat.ld, wo.p(), wo.ld, self.AH.p(), self.AH.ld, R, H, 2 * Hp,
+                      addend=e.pp("decoder.attn.linear_out.bias"), ld_add=H, add_rows=1)
+            return
+        q, ldq = (self.Q.p(), self.Q.ld) if d.attn == "general" else (cat.p(0, Hp), cat.ld)      # dot: the query is the decoder output
+        if d.attn == "general":
+            self.gemm(L.GEMM_NT, cat.p(0, Hp), cat.ld, wa.p(), wa.ld, self.Q.p(), self.Q.ld, R, H, H)
+        L.check(lib.vmmt_attn_fwd(dt, q, ldq, self.ctx, self.ctx_ld, self.src_len.data_ptr(), cat.p(), cat.ld,
                                   self.probs.data_ptr(), 1, R, self.S, Hp, st), "vmmt_attn_fwd")
         self.gemm(L.GEMM_NT, cat.p(), cat.ld, wo.p(), wo.ld, self.AH.p(), self.AH.ld, R, H, 2 * Hp, act=L.ACT_TANH)
 
@@ -174,6 +191,7 @@ def greedy_decode(eng, src, src_len, max_len=50, bos=2, eos=None, check_every=16
         b["ctx"].t.copy_(enc.t[:b["ctx"].t.shape[0]])
         b["zx"].t[:B].copy_(ws.zx.t[:B])
         b["src_len"].copy_(ws.src_len)
+        sp.prepare()
         tok[0].fill_(bos)
         b["counter"].zero_()
         # decoder state: h0 / c0 = encoder final states (Models.py:1158-1165)
@@ -241,6 +259,7 @@ def beam_decode(eng, src, src_len, beam_size, max_len=100, min_length=0, bos=2, 
         b["ctx"].t[:S * R].view(S, K, B, -1).copy_(enc.t[:S * B].view(S, 1, B, -1).expand(S, K, B, enc.ld))
         b["zx"].t[:R].view(K, B, -1).copy_(ws.zx.t[:B].unsqueeze(0).expand(K, B, ws.zx.ld))
         b["src_len"].view(K, B).copy_(ws.src_len.view(1, B).expand(K, B))
+        sp.prepare()
         for l in range(Lyr):
             sp.c[l][0].t[:R].view(K, B, -1).copy_(ws.cn[l].t[:B].unsqueeze(0).expand(K, B, ws.cn[l].ld))
             hb, ho = sp.h_buf(l, 0)

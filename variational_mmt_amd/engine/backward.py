@@ -208,21 +208,39 @@ class BackwardPlan(object):
                 self._comb_dO_entry = len(P)
                 self._patch["comb_dO"] = (len(P), 10)
                 e._call(P, lib.vmmt_gen_fwd_combine_dO, *self._combine_args)
-            e._call(P, lib.vmmt_act_bwd, dt, L.ACT_TANH, self.dO32.p(), self.dO32.ld, 1, self.AH.p(), self.AH.ld,
+            mlp = d.attn == "mlp"            # (no tanh behind linear_out: the activation backward is the dropout mask alone)
+            e._call(P, lib.vmmt_act_bwd, dt, L.ACT_NONE if mlp else L.ACT_TANH, self.dO32.p(), self.dO32.ld, 1, self.AH.p(), self.AH.ld,
                     self.out_mask.p() if drop else None, self.out_mask.ld if drop else 0, self.dPre.p(), self.dPre.ld, M, H)
             e._record(P, "dPre")
             wo, wa = e.sh["wo"], e.sh["wa"]
             e._gemm(P, L.GEMM_NN, self.dPre.p(), self.dPre.ld, wo.p(), wo.ld, self.dcat.p(), self.dcat.ld, M, 2 * Hp, H)
             ctx = self.enc_out[Lyr - 1]
-            if S > 64 or Tp > 64:
+            q, ldq = (self.cat.p(0, Hp), self.cat.ld) if d.attn == "dot" else (self.Q.p(), self.Q.ld)
+            if mlp:
+                # dWQ (into dQ), dUH, the direct part of dctx and the partial rows of dv in one launch; then dR = dWQ W_q + dcat[:, H:]
+                # (below, W_q in wa's place), dctx = dUH W_c + direct part, and the three small column sums
+                wc = e.sh["wc"]
+                if not hasattr(self, "dUH"):
+                    self.dUH, self.dctx_direct = Buf(S * B, H, e.T, e.dev), Buf(S * B, H, e.T, e.dev)
+                    self.dv_part = torch.zeros(lib.vmmt_attn_mlp_dv_parts(B, Hp), Hp, dtype=torch.float32, device=e.dev)
+                e._call(P, lib.vmmt_attn_mlp_bwd, dt, self.dcat.p(), self.dcat.ld, self.probs.data_ptr(), self.Q.p(), self.Q.ld,
+                        e.sh["attn_bq"].p(), self.UH.p(), self.UH.ld, e.sh["attn_v"].p(), ctx.p(), ctx.ld,
+                        self.src_len.data_ptr(), self.dQ.p(), self.dQ.ld, self.dUH.p(), self.dUH.ld, self.dctx_direct.p(),
+                        self.dctx_direct.ld, self.dv_part.data_ptr(), Tp, B, S, Hp)
+                e._gemm(P, L.GEMM_NN, self.dUH.p(), self.dUH.ld, wc.p(), wc.ld, self.dctx.p(), self.dctx.ld, S * B, H, H,
+                        addend=self.dctx_direct.p(), ld_add=self.dctx_direct.ld, add_rows=-1, add_is_T=1)
+                e._call(P, lib.vmmt_colsum, L.F32, self.dv_part.data_ptr(), Hp, self.dv_part.shape[0], H, 0, 0, e.gp("decoder.attn.v.weight"), None)
+                e._call(P, lib.vmmt_colsum, dt, self.dQ.p(), self.dQ.ld, M, H, 0, 0, e.gp("decoder.attn.linear_query.bias"), None)
+                e._call(P, lib.vmmt_colsum, dt, self.dPre.p(), self.dPre.ld, M, H, 0, 0, e.gp("decoder.attn.linear_out.bias"), None)
+            elif S > 64 or Tp > 64:
                 # longer than the per-sentence kernels take (S <= 64, T' <= 64): one wave per query / per source position
                 if not hasattr(self, "attn_dots"):
                     self.attn_dots = torch.zeros(M, dtype=torch.float32, device=e.dev)
-                e._call(P, lib.vmmt_attn_bwd_long, dt, self.dcat.p(), self.dcat.ld, self.probs.data_ptr(), self.Q.p(), self.Q.ld, ctx.p(),
+                e._call(P, lib.vmmt_attn_bwd_long, dt, self.dcat.p(), self.dcat.ld, self.probs.data_ptr(), q, ldq, ctx.p(),
                         ctx.ld, self.src_len.data_ptr(), self.dQ.p(), self.dQ.ld, self.dctx.p(), self.dctx.ld, Tp, B, S, Hp,
                         self.attn_dots.data_ptr())
             else:
-                e._call(P, lib.vmmt_attn_bwd, dt, self.dcat.p(), self.dcat.ld, self.probs.data_ptr(), self.Q.p(), self.Q.ld, ctx.p(), ctx.ld,
+                e._call(P, lib.vmmt_attn_bwd, dt, self.dcat.p(), self.dcat.ld, self.probs.data_ptr(), q, ldq, ctx.p(), ctx.ld,
                         self.src_len.data_ptr(), self.dQ.p(), self.dQ.ld, self.dctx.p(), self.dctx.ld, Tp, B, S, Hp)
             e._record(P, "dQ")
             e._gemm(P, L.GEMM_NN, self.dQ.p(), self.dQ.ld, wa.p(), wa.ld, self.dR.p(), self.dR.ld, M, H, H,
@@ -294,8 +312,15 @@ class BackwardPlan(object):
         e._gemm(P, L.GEMM_TN, self.dPre.p(), self.dPre.ld, self.cat.p(), self.cat.ld, e.gp("decoder.attn.linear_out.weight"), 2 * H,
                 H, 2 * Hp, M, out_f32=1, split_k=-1, cmap=(Hp, H), group=grp)
         e._wait(P, "dQ")
-        e._gemm(P, L.GEMM_TN, self.dQ.p(), self.dQ.ld, self.cat.p(0, Hp), self.cat.ld, e.gp("decoder.attn.linear_in.weight"), H,
-                H, H, M, out_f32=1, split_k=-1, group=grp)
+        if d.attn == "general":
+            e._gemm(P, L.GEMM_TN, self.dQ.p(), self.dQ.ld, self.cat.p(0, Hp), self.cat.ld, e.gp("decoder.attn.linear_in.weight"), H,
+                    H, H, M, out_f32=1, split_k=-1, group=grp)
+        elif d.attn == "mlp":                    # dW_q = dWQ^T r, dW_c = dUH^T Hs
+            mem = self.enc_out[Lyr - 1]
+            e._gemm(P, L.GEMM_TN, self.dQ.p(), self.dQ.ld, self.cat.p(0, Hp), self.cat.ld, e.gp("decoder.attn.linear_query.weight"), H,
+                    H, H, M, out_f32=1, split_k=-1, group=grp)
+            e._gemm(P, L.GEMM_TN, self.dUH.p(), self.dUH.ld, mem.p(), mem.ld, e.gp("decoder.attn.linear_context.weight"), H,
+                    H, H, S * B, out_f32=1, split_k=-1, group=grp)
         e._gemm_group(P, grp)
         # (the decoder's weight gradients held back until the encoder's backward recurrence is through -- both backward recurrences
         #  without guests, everything in the tail -- was measured in round 4: 1.80 against 1.735 ms per step; LABNOTES.md)

@@ -595,7 +595,18 @@ class Engine(StepAPI):
                    src2="decoder.rnn.bias_hh_l%d" % l, gate=gd)
             shadow("dec_whh_l%d" % l, 4 * d.hp, d.hid, "decoder.rnn.weight_hh_l%d" % l, gate=gd)
             shadow("dec_whhT_l%d" % l, d.hid, 4 * d.hp, "decoder.rnn.weight_hh_l%d" % l, transpose=True, gate=gd)
-        shadow("wa", d.hid, d.hid, "decoder.attn.linear_in.weight")
+        if d.attn == "general":
+            shadow("wa", d.hid, d.hid, "decoder.attn.linear_in.weight")
+        elif d.attn == "mlp":                # W_q takes linear_in's place (both multiply the decoder output); W_c multiplies the memory
+            shadow("wa", d.hid, d.hid, "decoder.attn.linear_query.weight")
+            shadow("wc", d.hid, d.hid, "decoder.attn.linear_context.weight")
+            # b_q and v as the kernels read them: f32, `hp` wide with zeros in the padding (v = 0 there: a padded lane adds nothing to a
+            # score or to any gradient), so that a hidden size of 500 runs the LDS / MFMA kernels at 512 as `general` does
+            shadow("attn_bq", 1, d.hp, "decoder.attn.linear_query.bias", dtype=torch.float32)
+            shadow("attn_v", 1, d.hp, "decoder.attn.v.weight", dtype=torch.float32)
+        else:                                # dot: q = r.  The backward's dR = dQ + dcat[:, H:] runs through the GEMM that `general` uses, with I
+            self.sh["wa"] = Buf(d.hid, d.hid, T, dev)
+            self.sh["wa"].t[:d.hid, :d.hid] = torch.eye(d.hid, dtype=T, device=dev)
         # W_out [H][2H] multiplies [c ; r] (GlobalAttention.py:187); the two halves of that buffer start at 0 and hp
         if d.hp == d.hid:
             shadow("wo", d.hid, 2 * d.hid, "decoder.attn.linear_out.weight")

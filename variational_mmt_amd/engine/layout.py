@@ -16,7 +16,11 @@ def _ru(x, m):
 
 
 class Dims(object):
-    def __init__(self, vs, vt, emb=500, hid=500, z=500, img=2048, layers=2, brnn=False, dropout=0.0, conditional=False):
+    def __init__(self, vs, vt, emb=500, hid=500, z=500, img=2048, layers=2, brnn=False, dropout=0.0, conditional=False, attn="general"):
+        assert attn in ("general", "dot", "mlp"), attn          # -global_attention (onmt/modules/GlobalAttention.py:70-78)
+        if attn != "general" and conditional:
+            raise NotImplementedError("-global_attention %s with --conditional is not built (the conditional plans keep `general`)" % attn)
+        self.attn = attn
         self.vs, self.vt, self.emb, self.hid, self.z, self.img = vs, vt, emb, hid, z, img
         self.layers, self.brnn, self.dropout = layers, bool(brnn), float(dropout)
         self.conditional = bool(conditional)       # --conditional prior (ModelConstructor.py:435-460)
@@ -48,7 +52,13 @@ class Dims(object):
         d = self
         s = []
         s += [("generator.0.weight", (d.vt, d.hid)), ("generator.0.bias", (d.vt,))]
-        s += [("decoder.attn.linear_out.weight", (d.hid, 2 * d.hid)), ("decoder.attn.linear_in.weight", (d.hid, d.hid))]
+        s += [("decoder.attn.linear_out.weight", (d.hid, 2 * d.hid))]       # first of its segment (Engine: seg_starts)
+        if d.attn == "general":
+            s += [("decoder.attn.linear_in.weight", (d.hid, d.hid))]
+        elif d.attn == "mlp":                # GlobalAttention.py:70-78; linear_out has a bias for mlp only
+            s += [("decoder.attn.linear_out.bias", (d.hid,)), ("decoder.attn.linear_query.weight", (d.hid, d.hid)),
+                  ("decoder.attn.linear_query.bias", (d.hid,)), ("decoder.attn.linear_context.weight", (d.hid, d.hid)),
+                  ("decoder.attn.v.weight", (1, d.hid))]
         for l in reversed(range(d.layers)):
             i = d.emb + d.z if l == 0 else d.hid
             s += [("decoder.rnn.weight_ih_l%d" % l, (4 * d.hid, i)), ("decoder.rnn.weight_hh_l%d" % l, (4 * d.hid, d.hid)),

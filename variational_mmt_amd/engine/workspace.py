@@ -464,10 +464,31 @@ class Workspace(BackwardPlan, ConditionalPlans):
                     x = self.dec_xdrop[l]
         # a7 attention
         wa, wo = e.sh["wa"], e.sh["wo"]
-        e._gemm(P, L.GEMM_NT, self.cat.p(0, Hp), self.cat.ld, wa.p(), wa.ld, self.Q.p(), self.Q.ld, M, H, H)
-        e._call(P, lib.vmmt_attn_fwd, dt, self.Q.p(), self.Q.ld, ctx.p(), ctx.ld, self.src_len.data_ptr(), self.cat.p(), self.cat.ld,
-                self.probs.data_ptr(), Tp, B, S, Hp)
-        e._gemm(P, L.GEMM_NT, self.cat.p(), self.cat.ld, wo.p(), wo.ld, self.AH.p(), self.AH.ld, M, H, 2 * Hp, act=L.ACT_TANH)
+        if d.attn == "mlp":
+            # GlobalAttention.py:114-127: WQ = r W_q^T (into Q), UH = Hs W_c^T, score = v . tanh(WQ + b_q + UH); linear_out has a bias
+            # and no tanh behind it (:187-190)
+            if training and (S > 64 or Tp > 64):
+                raise ValueError("-global_attention mlp trains on batches of at most 64 source positions and 64 target steps "
+                                 "(got S = %d, T' = %d): the mlp attention has no long-sequence backward" % (S, Tp))
+            if not hasattr(self, "UH"):
+                self.UH = Buf(S * B, H, e.T, e.dev)
+            wc = e.sh["wc"]
+            e._gemm(P, L.GEMM_NT, self.cat.p(0, Hp), self.cat.ld, wa.p(), wa.ld, self.Q.p(), self.Q.ld, M, H, H)
+            e._gemm(P, L.GEMM_NT, ctx.p(), ctx.ld, wc.p(), wc.ld, self.UH.p(), self.UH.ld, S * B, H, H)
+            e._call(P, lib.vmmt_attn_mlp_fwd, dt, self.Q.p(), self.Q.ld, e.sh["attn_bq"].p(), self.UH.p(), self.UH.ld,
+                    e.sh["attn_v"].p(), ctx.p(), ctx.ld, self.src_len.data_ptr(), self.cat.p(), self.cat.ld,
+                    self.probs.data_ptr(), Tp, B, S, Hp)
+            e._gemm(P, L.GEMM_NT, self.cat.p(), self.cat.ld, wo.p(), wo.ld, self.AH.p(), self.AH.ld, M, H, 2 * Hp,
+                    addend=e.pp("decoder.attn.linear_out.bias"), ld_add=H, add_rows=1)
+        else:
+            if d.attn == "general":
+                e._gemm(P, L.GEMM_NT, self.cat.p(0, Hp), self.cat.ld, wa.p(), wa.ld, self.Q.p(), self.Q.ld, M, H, H)
+                q, ldq = self.Q.p(), self.Q.ld
+            else:                                # dot: the query is the decoder output itself, the right half of [c ; r]
+                q, ldq = self.cat.p(0, Hp), self.cat.ld
+            e._call(P, lib.vmmt_attn_fwd, dt, q, ldq, ctx.p(), ctx.ld, self.src_len.data_ptr(), self.cat.p(), self.cat.ld,
+                    self.probs.data_ptr(), Tp, B, S, Hp)
+            e._gemm(P, L.GEMM_NT, self.cat.p(), self.cat.ld, wo.p(), wo.ld, self.AH.p(), self.AH.ld, M, H, 2 * Hp, act=L.ACT_TANH)
         # join: the loss plans read mu_v.  ONE wait for everything the other streams did in this plan -- `img_fwd` is the side stream's last
         # record: the mask (`out_mask`, recorded before it on that stream, or on the aux stream which that stream joined: `aux_fwd`) and both
         # halves of the last optimiser step (issued on those streams in front of this plan's work) are behind it.  Every wait costs the main

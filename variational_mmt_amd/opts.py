@@ -91,7 +91,7 @@ _MODEL = [
         ("-context_gate", str, None, dict(choices=["source", "target", "both"], help="context gate (not on the MI355X path)")),
     ]),
     ("Model- Attention", [
-        ("-global_attention", str, "general", dict(choices=["dot", "general", "mlp"], help="attention score; 'general' (Luong) on the MI355X path")),
+        ("-global_attention", str, "general", dict(choices=["dot", "general", "mlp"], help="attention score: dot, general (Luong) or mlp (Bahdanau); dot and mlp not with --conditional")),
         ("-copy_attn", "flag", None, dict(help="copy attention (not on the MI355X path)")),
         ("-copy_attn_force", "flag", None, dict(help="force copying")),
         ("-reuse_copy_attn", "flag", None, dict(help="reuse the standard attention for copying")),
