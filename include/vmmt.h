@@ -249,6 +249,19 @@ int vmmt_attn_mlp_bwd(int dtype, const void* dcat, int64_t lddc, const float* pr
                       const void* uh, int64_t lduh, const float* v, const void* ctx, int64_t ldc, const int64_t* lens, void* dwq,
                       int64_t lddwq, void* duh, int64_t ldduh, void* dctx, int64_t lddx, float* dv_part, int Tp, int B, int S,
                       int H, void* stream);
+/* backward beyond the per-sentence kernel (GlobalAttention.py:114-127,171-184 differentiated, as above): the operands and the
+ * outputs of vmmt_attn_mlp_bwd, for 1 <= S <= 256, any T' >= 1, H <= 1024 (VMMT_EINVAL beyond, and where the sizes below do not
+ * fit an int).  Four launches: dS per (sentence, 32 queries); the tanh part per (sentence, 256 columns, chunk of queries) with
+ * one f32 partial of duh and dv per chunk; dctx per (sentence, 256 columns, 64 positions); the fold of duh in chunk order.
+ * Nothing is allocated: `scratch` holds vmmt_attn_mlp_bwd_long_scratch(Tp, B, S, H) floats and dv_part is
+ * f32 [vmmt_attn_mlp_bwd_long_dv_parts(Tp, B, H)][H] (every entry written, folded by the caller with vmmt_colsum); both
+ * helpers return 0 for sizes they cannot express.  No floating-point atomics: the result is bit-reproducible. */
+int vmmt_attn_mlp_bwd_long_scratch(int Tp, int B, int S, int H);
+int vmmt_attn_mlp_bwd_long_dv_parts(int Tp, int B, int H);
+int vmmt_attn_mlp_bwd_long(int dtype, const void* dcat, int64_t lddc, const float* probs, const void* wq, int64_t ldwq,
+                           const float* bq, const void* uh, int64_t lduh, const float* v, const void* ctx, int64_t ldc,
+                           const int64_t* lens, void* dwq, int64_t lddwq, void* duh, int64_t ldduh, void* dctx, int64_t lddx,
+                           float* dv_part, int Tp, int B, int S, int H, float* scratch, void* stream);
 /* hbar[b] = mean_{s<len_b} ctx[s][b]  (GlobalInferenceNetwork.encode_seq, modules/NormalVariationalEncoder.py:65-84) */
 int vmmt_masked_mean(int dtype, const void* ctx, int64_t ldc, const int64_t* lens, void* out, int64_t ldo, int B, int S,
                      int H, void* stream);

@@ -87,6 +87,9 @@ _SIGS = {
     "vmmt_attn_mlp_fwd": (i32, [i32, vp, i64, vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, i32, i32, i32, i32, vp]),
     "vmmt_attn_mlp_dv_parts": (i32, [i32, i32]),
     "vmmt_attn_mlp_bwd": (i32, [i32, vp, i64, vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, i64, vp, i64, vp, i32, i32, i32, i32, vp]),
+    "vmmt_attn_mlp_bwd_long_scratch": (i32, [i32, i32, i32, i32]),
+    "vmmt_attn_mlp_bwd_long_dv_parts": (i32, [i32, i32, i32]),
+    "vmmt_attn_mlp_bwd_long": (i32, [i32, vp, i64, vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, i64, vp, i64, vp, i32, i32, i32, i32, vp, vp]),
     "vmmt_masked_mean": (i32, [i32, vp, i64, vp, vp, i64, i32, i32, i32, vp]),
     "vmmt_gen_npart": (i32, [i32]),
     "vmmt_gen_argmax": (i32, [vp, vp, i32, i32, vp, vp, vp]),

@@ -220,13 +220,21 @@ class BackwardPlan(object):
                 # dWQ (into dQ), dUH, the direct part of dctx and the partial rows of dv in one launch; then dR = dWQ W_q + dcat[:, H:]
                 # (below, W_q in wa's place), dctx = dUH W_c + direct part, and the three small column sums
                 wc = e.sh["wc"]
+                long_ = S > 64 or Tp > 64        # beyond the per-sentence kernel: dS, tanh part per chunk of queries, dHs, fold
                 if not hasattr(self, "dUH"):
                     self.dUH, self.dctx_direct = Buf(S * B, H, e.T, e.dev), Buf(S * B, H, e.T, e.dev)
-                    self.dv_part = torch.zeros(lib.vmmt_attn_mlp_dv_parts(B, Hp), Hp, dtype=torch.float32, device=e.dev)
-                e._call(P, lib.vmmt_attn_mlp_bwd, dt, self.dcat.p(), self.dcat.ld, self.probs.data_ptr(), self.Q.p(), self.Q.ld,
+                    parts = lib.vmmt_attn_mlp_bwd_long_dv_parts(Tp, B, Hp) if long_ else lib.vmmt_attn_mlp_dv_parts(B, Hp)
+                    self.dv_part = torch.zeros(parts, Hp, dtype=torch.float32, device=e.dev)
+                    if long_:
+                        self.attn_scratch = torch.zeros(lib.vmmt_attn_mlp_bwd_long_scratch(Tp, B, S, Hp), dtype=torch.float32, device=e.dev)
+                args = (dt, self.dcat.p(), self.dcat.ld, self.probs.data_ptr(), self.Q.p(), self.Q.ld,
                         e.sh["attn_bq"].p(), self.UH.p(), self.UH.ld, e.sh["attn_v"].p(), ctx.p(), ctx.ld,
                         self.src_len.data_ptr(), self.dQ.p(), self.dQ.ld, self.dUH.p(), self.dUH.ld, self.dctx_direct.p(),
                         self.dctx_direct.ld, self.dv_part.data_ptr(), Tp, B, S, Hp)
+                if long_:
+                    e._call(P, lib.vmmt_attn_mlp_bwd_long, *args, self.attn_scratch.data_ptr())
+                else:
+                    e._call(P, lib.vmmt_attn_mlp_bwd, *args)
                 e._gemm(P, L.GEMM_NN, self.dUH.p(), self.dUH.ld, wc.p(), wc.ld, self.dctx.p(), self.dctx.ld, S * B, H, H,
                         addend=self.dctx_direct.p(), ld_add=self.dctx_direct.ld, add_rows=-1, add_is_T=1)
                 e._call(P, lib.vmmt_colsum, L.F32, self.dv_part.data_ptr(), Hp, self.dv_part.shape[0], H, 0, 0, e.gp("decoder.attn.v.weight"), None)

@@ -467,9 +467,13 @@ class Workspace(BackwardPlan, ConditionalPlans):
         if d.attn == "mlp":
             # GlobalAttention.py:114-127: WQ = r W_q^T (into Q), UH = Hs W_c^T, score = v . tanh(WQ + b_q + UH); linear_out has a bias
             # and no tanh behind it (:187-190)
-            if training and (S > 64 or Tp > 64):
-                raise ValueError("-global_attention mlp trains on batches of at most 64 source positions and 64 target steps "
-                                 "(got S = %d, T' = %d): the mlp attention has no long-sequence backward" % (S, Tp))
+            # (raised here, when the plan is built, not by the first launch's return code)
+            if S > 256:
+                raise ValueError("-global_attention mlp takes batches of at most 256 source positions (got S = %d): "
+                                 "the mlp attention kernels hold a source sentence's positions in one wave's lanes, four each" % S)
+            if training and (S > 64 or Tp > 64) and lib.vmmt_attn_mlp_bwd_long_scratch(Tp, B, S, Hp) <= 0:
+                raise ValueError("-global_attention mlp: the backward's scratch for S = %d, T' = %d, B = %d exceeds 2^31 floats; "
+                                 "use a smaller batch" % (S, Tp, B))
             if not hasattr(self, "UH"):
                 self.UH = Buf(S * B, H, e.T, e.dev)
             wc = e.sh["wc"]
