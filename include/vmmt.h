@@ -167,6 +167,56 @@ int vmmt_lstm_chain_fwd(int dtype, int ndir, int nsteps, const vmmt_lstm_dir_fwd
 int vmmt_lstm_chain_bwd(int dtype, int ndir, int nsteps, const vmmt_lstm_dir_bwd* dirs, const int64_t* lens, int B, int H,
                         int mode, void* stream);
 
+/* ---- GRU time steps (-rnn_type GRU) -----------------------------------------------------------------------------
+ * The reference builds its recurrences with getattr(nn, rnn_type) (encoder onmt/Models.py:124-129,140-147 incl.
+ * pack_padded_sequence; decoder StdRNNVIModel1Decoder._build_rnn, onmt/VI_Model1.py:137-152), so these replace cuDNN's GRU.
+ * One launch per time step, both directions in one launch; the input projection of the whole sequence is a vmmt_gemm.
+ * torch nn.GRU, gate order r,z,n:
+ *   r = sigmoid(gx_r + h W_hr^T) ; z = sigmoid(gx_z + h W_hz^T) ; hn = h W_hn^T + b_hn ; n = tanh(gx_n + r hn) ; h' = n + z (h - n)
+ * gx = x W_ih^T + b_ih with b_hh's r and z parts folded in; b_hn is scaled by r and therefore an operand of the step.
+ * Column layout of gx / dgx / dgh: gate-major, g*H + u (== torch's weight row order); `saved` has a fourth block, hn.
+ * A GRU has no cell state: the state is the output row (zero at padded positions), so h_prev of a step is h_out of the step
+ * before -- never the same buffer as h_out -- and the reverse direction starts from zero at a sentence's last token. */
+typedef struct vmmt_gru_dir_fwd {
+  const void* h_prev; int64_t ld_hprev;  /* T   [B][ld]  state entering the step                               */
+  const void* w_hh;   int64_t ld_w;      /* T   [3H][ld] recurrent weight, k contiguous                         */
+  const void* gx;     int64_t ld_gx;     /* f32 [B][ld]  row block of step t (3H columns)                       */
+  const void* gx2;    int64_t ld_gx2;    /* f32 [B][ld]  optional per-sentence addend (z W_z^T; VI_Model1.py:99-100) */
+  const void* b_hn;                      /* f32 [H]      bias_hh's n part                                       */
+  void* saved;        int64_t ld_saved;  /* T   [B][ld]  out: r, z, n, hn (4H columns, for the backward)        */
+  void* h_out;        int64_t ld_h;      /* T   [B][ld]  out: h' (zero at padded positions)                     */
+  void* h_n;          int64_t ld_hn;     /* T   [B][ld]  out (optional): final state, see `capture`             */
+  int t;                                 /* time index (compared with lens[b])                                  */
+  int capture;                           /* 0 none; 1 if t == lens[b]-1; 2 if t == 0; 3 always                  */
+} vmmt_gru_dir_fwd;
+int vmmt_gru_step_fwd(int dtype, int ndir, const vmmt_gru_dir_fwd* dirs, const int64_t* lens, int B, int H, void* stream);
+
+/* backward of one step.  mode 0: dh = dgh_next W_hh + dh_above + dh_carry (+ dh_n when injected); writes the input-side gate
+ * gradients dgx_out = [dr, dz, dn] (for dW_ih, db_ih, dx), the recurrent-side ones dgh_out = [dr, dz, dn r] (for dW_hh, db_hh and
+ * the next step's recurrent term) and dh_carry = dh z (the direct path h -> h').  Padded positions write zeros to all three.
+ * mode 1: only dh0_out = dgh_next W_hh + dh_carry (gradient of the initial state; dh_carry may be NULL).  No atomics. */
+typedef struct vmmt_gru_dir_bwd {
+  const void* dgh_next; int64_t ld_dgn;  /* T [B][ld] dgh_out of the step processed just before (NULL = none)   */
+  const void* w_hh_t;   int64_t ld_wt;   /* T [H][ld]: W_hh transposed (k = gate row index contiguous, 3H)      */
+  const void* dh_above; int64_t ld_dha;  /* T [B][ld] or NULL                                                   */
+  const void* saved;    int64_t ld_saved;/* T: r, z, n, hn of step t                                            */
+  const void* h_prev;   int64_t ld_hp;   /* T: the state that entered step t (NULL = zeros)                     */
+  void* dh_carry;       int64_t ld_dhc;  /* f32 in/out                                                          */
+  void* dgx_out;        int64_t ld_dgx;  /* T [B][ld], 3H columns                                               */
+  void* dgh_out;        int64_t ld_dgh;  /* T [B][ld], 3H columns                                               */
+  const void* dh_n;     int64_t ld_dhn;  /* f32 or NULL: gradient of the captured final h                       */
+  void* dh0_out;        int64_t ld_dh0;  /* f32, mode 1                                                         */
+  int t;
+  int inject;                            /* 0 none; 1 if t == lens[b]-1; 2 if t == 0; 3 always                  */
+} vmmt_gru_dir_bwd;
+int vmmt_gru_step_bwd(int dtype, int ndir, const vmmt_gru_dir_bwd* dirs, const int64_t* lens, int B, int H, int mode,
+                      void* stream);
+/* a whole recurrence in one host call (nn.GRU's time loop): nsteps launches, step i described by dirs[i*ndir .. (i+1)*ndir) */
+int vmmt_gru_chain_fwd(int dtype, int ndir, int nsteps, const vmmt_gru_dir_fwd* dirs, const int64_t* lens, int B, int H,
+                       void* stream);
+int vmmt_gru_chain_bwd(int dtype, int ndir, int nsteps, const vmmt_gru_dir_bwd* dirs, const int64_t* lens, int B, int H,
+                       int mode, void* stream);
+
 /* a whole FORWARD recurrence in ONE LAUNCH (persistent kernel): every workgroup (16 sentences x 32 hidden units) keeps its W_hh slice in
  * registers for the whole sequence and the workgroups of a 16-sentence row group hand h_t to each other in-launch as tagged 8-byte granules
  * ({two bf16 | tag}, one sc1 write-through store each; consumers re-read with sc1 loads until the tags match; bounded spins).

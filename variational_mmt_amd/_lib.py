@@ -51,6 +51,19 @@ class LstmDirBwd(C.Structure):
                 ("t", i32), ("inject", i32)]
 
 
+class GruDirFwd(C.Structure):
+    _fields_ = [("h_prev", vp), ("ld_hprev", i64), ("w_hh", vp), ("ld_w", i64), ("gx", vp), ("ld_gx", i64), ("gx2", vp), ("ld_gx2", i64),
+                ("b_hn", vp), ("saved", vp), ("ld_saved", i64), ("h_out", vp), ("ld_h", i64), ("h_n", vp), ("ld_hn", i64),
+                ("t", i32), ("capture", i32)]
+
+
+class GruDirBwd(C.Structure):
+    _fields_ = [("dgh_next", vp), ("ld_dgn", i64), ("w_hh_t", vp), ("ld_wt", i64), ("dh_above", vp), ("ld_dha", i64),
+                ("saved", vp), ("ld_saved", i64), ("h_prev", vp), ("ld_hp", i64), ("dh_carry", vp), ("ld_dhc", i64),
+                ("dgx_out", vp), ("ld_dgx", i64), ("dgh_out", vp), ("ld_dgh", i64), ("dh_n", vp), ("ld_dhn", i64),
+                ("dh0_out", vp), ("ld_dh0", i64), ("t", i32), ("inject", i32)]
+
+
 class ZeroDesc(C.Structure):
     _fields_ = [("ptr", vp), ("bytes", i64), ("chunk_start", i64)]
 
@@ -81,6 +94,10 @@ _SIGS = {
     "vmmt_lstm_seq_xchg_bytes_bwd": (i64, [i32, i32, i32]),
     "vmmt_lstm_seq_bwd": (i32, [i32, i32, i32, C.POINTER(LstmDirBwd), vp, vp, i32, i32, i32, vp, vp, vp]),
     "vmmt_lstm_chain_bwd": (i32, [i32, i32, i32, C.POINTER(LstmDirBwd), vp, i32, i32, i32, vp]),
+    "vmmt_gru_step_fwd": (i32, [i32, i32, C.POINTER(GruDirFwd), vp, i32, i32, vp]),
+    "vmmt_gru_step_bwd": (i32, [i32, i32, C.POINTER(GruDirBwd), vp, i32, i32, i32, vp]),
+    "vmmt_gru_chain_fwd": (i32, [i32, i32, i32, C.POINTER(GruDirFwd), vp, i32, i32, vp]),
+    "vmmt_gru_chain_bwd": (i32, [i32, i32, i32, C.POINTER(GruDirBwd), vp, i32, i32, i32, vp]),
     "vmmt_attn_fwd": (i32, [i32, vp, i64, vp, i64, vp, vp, i64, vp, i32, i32, i32, i32, vp]),
     "vmmt_attn_bwd": (i32, [i32, vp, i64, vp, vp, i64, vp, i64, vp, vp, i64, vp, i64, i32, i32, i32, i32, vp]),
     "vmmt_attn_bwd_long": (i32, [i32, vp, i64, vp, vp, i64, vp, i64, vp, vp, i64, vp, i64, i32, i32, i32, i32, vp, vp]),

@@ -32,9 +32,10 @@ class _Stepper(object):
         Hp = d.hp                       # hidden size as computed (engine.Dims.hp): gate g at column g * Hp, [c ; h] halves at 0 / Hp
         nb = lambda r, c, t=T: Buf(r, c, t, dev)
         self.X = nb(R, E)
-        self.gx = [nb(R, 4 * Hp, f32) for _ in range(Lyr)]
+        self.gru = d.rnn == "GRU"       # (-rnn_type GRU: three gate blocks, the state is h alone)
+        self.gx = [nb(R, d.gates * Hp, f32) for _ in range(Lyr)]
         self.gates = nb(R, 4 * Hp)
-        self.c = [[nb(R, H, f32), nb(R, H, f32)] for _ in range(Lyr)]
+        self.c = [] if self.gru else [[nb(R, H, f32), nb(R, H, f32)] for _ in range(Lyr)]
         self.h = [[nb(R, H), nb(R, H)] for _ in range(Lyr - 1)]
         self.cat = [nb(R, 2 * Hp), nb(R, 2 * Hp)]
         self.Q, self.AH = nb(R, H), nb(R, H)
@@ -70,15 +71,26 @@ class _Stepper(object):
             gx = self.gx[l]
             if l == 0:
                 we = e.sh["dec_wih_l0_e"]
-                self.gemm(L.GEMM_NT, x.p(0, xoff), x.ld, we.p(), we.ld, gx.p(), gx.ld, R, 4 * Hp, xcols, out_f32=1)
+                self.gemm(L.GEMM_NT, x.p(0, xoff), x.ld, we.p(), we.ld, gx.p(), gx.ld, R, d.gates * Hp, xcols, out_f32=1)
             else:
                 wi, bs = e.sh["dec_wih_l%d" % l], e.sh["dec_b_l%d" % l]
-                self.gemm(L.GEMM_NT, x.p(0, xoff), x.ld, wi.p(), wi.ld, gx.p(), gx.ld, R, 4 * Hp, xcols, addend=bs.p(), ld_add=bs.ld,
+                self.gemm(L.GEMM_NT, x.p(0, xoff), x.ld, wi.p(), wi.ld, gx.p(), gx.ld, R, d.gates * Hp, xcols, addend=bs.p(), ld_add=bs.ld,
                           add_rows=1, out_f32=1)
-            arr = (L.LstmDirFwd * 2)()
-            a = arr[0]
             hp, ho = self.h_buf(l, 0), self.h_buf(l, 1)
             whh = e.sh["dec_whh_l%d" % l]
+            if self.gru:
+                arr = (L.GruDirFwd * 2)()
+                a = arr[0]
+                a.h_prev, a.ld_hprev, a.w_hh, a.ld_w, a.gx, a.ld_gx = hp[0].p(0, hp[1]), hp[0].ld, whh.p(), whh.ld, gx.p(), gx.ld
+                if l == 0:
+                    a.gx2, a.ld_gx2 = self.zx, self.zx_ld        # z W_z^T + b_ih + b_hh's r and z parts
+                a.b_hn, a.saved, a.ld_saved = e.sh["dec_bhn_l%d" % l].p(), self.gates.p(), self.gates.ld
+                a.h_out, a.ld_h, a.t, a.capture = ho[0].p(0, ho[1]), ho[0].ld, t, 0
+                L.check(lib.vmmt_gru_step_fwd(dt, 1, arr, None, R, Hp, st), "vmmt_gru_step_fwd")
+                x, xoff, xcols = ho[0], ho[1], H
+                continue
+            arr = (L.LstmDirFwd * 2)()
+            a = arr[0]
             a.h_prev, a.ld_hprev = hp[0].p(0, hp[1]), hp[0].ld
             a.c_prev, a.ld_cprev = self.c[l][0].p(), self.c[l][0].ld
             a.w_hh, a.ld_w = whh.p(), whh.ld
@@ -114,7 +126,7 @@ class _Stepper(object):
         e = self.eng
         H, Lyr, st = e.d.hid, e.d.layers, e.stream()
         for l in range(Lyr):
-            pairs = [(self.h_buf(l, 1), self.h_buf(l, 0), e.tsz), ((self.c[l][1], 0), (self.c[l][0], 0), 4)]
+            pairs = [(self.h_buf(l, 1), self.h_buf(l, 0), e.tsz)] + ([] if self.gru else [((self.c[l][1], 0), (self.c[l][0], 0), 4)])
             for (sb, so), (db, do), esz in pairs:
                 if rows_ptr is None:
                     db.t[:self.R, do:do + H].copy_(sb.t[:self.R, so:so + H])
@@ -196,7 +208,8 @@ def greedy_decode(eng, src, src_len, max_len=50, bos=2, eos=None, check_every=16
         b["counter"].zero_()
         # decoder state: h0 / c0 = encoder final states (Models.py:1158-1165)
         for l in range(Lyr):
-            sp.c[l][0].view().copy_(ws.cn[l].view())
+            if not sp.gru:
+                sp.c[l][0].view().copy_(ws.cn[l].view())
             hb, ho = sp.h_buf(l, 0)
             hb.t[:B, ho:ho + H].copy_(ws.hn[l].view())
 
@@ -227,7 +240,7 @@ def beam_decode(eng, src, src_len, beam_size, max_len=100, min_length=0, bos=2, 
     key = ("beam", B, S, K, max_len, int(eos))
     b = eng.ws.get(key)
     if b is None:
-        b = dict(ctx=Buf(S * R, H, eng.T, dev), zx=Buf(R, 4 * d.hp, f32, dev), src_len=torch.zeros(R, dtype=i64, device=dev),
+        b = dict(ctx=Buf(S * R, H, eng.T, dev), zx=Buf(R, d.gates * d.hp, f32, dev), src_len=torch.zeros(R, dtype=i64, device=dev),
                  logits=Buf(R, V, f32, dev), tok=torch.zeros(2, R, dtype=i64, device=dev), sel=torch.zeros(R, dtype=i64, device=dev),
                  scores=torch.zeros(B, K, dtype=f32, device=dev), h_score=torch.zeros(max_len, B, K, dtype=f32, device=dev),
                  h_prev=torch.zeros(max_len, B, K, dtype=torch.int32, device=dev),
@@ -261,7 +274,8 @@ def beam_decode(eng, src, src_len, beam_size, max_len=100, min_length=0, bos=2, 
         b["src_len"].view(K, B).copy_(ws.src_len.view(1, B).expand(K, B))
         sp.prepare()
         for l in range(Lyr):
-            sp.c[l][0].t[:R].view(K, B, -1).copy_(ws.cn[l].t[:B].unsqueeze(0).expand(K, B, ws.cn[l].ld))
+            if not sp.gru:
+                sp.c[l][0].t[:R].view(K, B, -1).copy_(ws.cn[l].t[:B].unsqueeze(0).expand(K, B, ws.cn[l].ld))
             hb, ho = sp.h_buf(l, 0)
             hb.t[:R, ho:ho + H].view(K, B, H).copy_(ws.hn[l].view().unsqueeze(0).expand(K, B, H))
         tok[0].fill_(pad)                         # Beam.__init__: next_ys[0] = [bos, pad, pad, ...] (Beam.py:34-36)

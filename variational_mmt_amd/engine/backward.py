@@ -17,7 +17,9 @@ class BackwardPlan(object):
         e, d, lib = self.e, self.e.d, self.e.lib
         B, S, Tp, M, MS = self.B, self.S, self.Tp, self.M, self.MS
         H, Hd, E, Z, D, V, Lyr, dirs = d.hid, d.hd, d.emb, d.z, d.img, d.vt, d.layers, d.dirs
-        Hp, Hdp = d.hp, d.hdp
+        Hp, Hdp, G = d.hp, d.hdp, d.gates
+        gru = d.rnn == "GRU"
+        db_in_gemm = e.lstm_db_in_gemm and not gru      # (one column sum serves b_ih and b_hh of an LSTM only: the GRU's n parts differ)
         gmap_d, gmap_e = (Hp, H), (Hdp, Hd)       # padded gate blocks -> nn.LSTM's [4H] rows (vmmt_gemm_args.c_row_blk)
         dt = e.dt
         P = []
@@ -340,8 +342,20 @@ class BackwardPlan(object):
             outb, ocol = (self.cat, Hp) if last else (self.dec_out[l], 0)
             whhT = e.sh["dec_whhT_l%d" % l]
             dg = self.dec_dgates[l]
-            seq = (L.LstmDirBwd * (Tp + 1))()                   # Tp cell-backward steps + the dh0 step
-            for i, t in enumerate(reversed(range(Tp))):
+            dgr = self.dec_dgh[l] if gru else dg               # recurrent-side gate gradients (GRU: [dr, dz, dn r]; LSTM: the same matrix)
+            seq = ((L.GruDirBwd if gru else L.LstmDirBwd) * (Tp + 1))()                   # Tp cell-backward steps + the dh0 step
+            for i, t in enumerate(reversed(range(Tp)) if gru else ()):
+                a = seq[i]
+                if t < Tp - 1:
+                    a.dgh_next, a.ld_dgn = dgr.p((t + 1) * B), dgr.ld
+                a.w_hh_t, a.ld_wt = whhT.p(), whhT.ld
+                a.dh_above, a.ld_dha = dh_above.p(t * B), dh_above.ld
+                a.saved, a.ld_saved = self.dec_gates[l].p(t * B), self.dec_gates[l].ld
+                a.h_prev, a.ld_hp = (outb.p((t - 1) * B, ocol), outb.ld) if t > 0 else (self.hn[l].p(), self.hn[l].ld)
+                a.dh_carry, a.ld_dhc = self.dec_dcc[l].p(), self.dec_dcc[l].ld       # the f32 direct path dh z, in the LSTM's dc buffer
+                a.dgx_out, a.ld_dgx, a.dgh_out, a.ld_dgh = dg.p(t * B), dg.ld, dgr.p(t * B), dgr.ld
+                a.t, a.inject = t, 0
+            for i, t in enumerate(() if gru else reversed(range(Tp))):
                 a = seq[i]
                 if t < Tp - 1:
                     a.dgates_next, a.ld_dgn = dg.p((t + 1) * B), dg.ld
@@ -357,16 +371,20 @@ class BackwardPlan(object):
                 a.dgates_out, a.ld_dgo = dg.p(t * B), dg.ld
                 a.t, a.inject = t, 0
             a = seq[Tp]                                        # gradient of the initial hidden state: dgates_0 W_hh (mode 1)
-            a.dgates_next, a.ld_dgn = dg.p(0), dg.ld
+            if gru:                                            # ... + the direct path left in the carry
+                a.dgh_next, a.ld_dgn = dgr.p(0), dgr.ld
+                a.dh_carry, a.ld_dhc = self.dec_dcc[l].p(), self.dec_dcc[l].ld
+            else:
+                a.dgates_next, a.ld_dgn = dg.p(0), dg.ld
             a.w_hh_t, a.ld_wt = whhT.p(), whhT.ld
             a.dh0_out, a.ld_dh0 = self.dec_dh0[l].p(), self.dec_dh0[l].ld
             # (conditional model: encoder_tgt's persistent backward is running by now; two persistent launches share a CU only if their
             #  registers fit one SIMD file and their LDS one CU -- 272 + 166 registers, 72 + 40 KiB here)
-            e._lstm_seq_bwd(P, seq, 1, Tp, None, B, Hp, with_dh0=1)
+            (e._gru_seq_bwd if gru else e._lstm_seq_bwd)(P, seq, 1, Tp, None, B, Hp, with_dh0=1)
             e._record(P, "dec_dg%d" % l)
             if l > 0:       # gradient w.r.t. the layer input stays on the critical path
                 wi = e.sh["dec_wih_l%d" % l]
-                e._gemm(P, L.GEMM_NN, dg.p(), dg.ld, wi.p(), wi.ld, self.dec_dx[l - 1].p(), self.dec_dx[l - 1].ld, M, H, 4 * Hp)
+                e._gemm(P, L.GEMM_NN, dg.p(), dg.ld, wi.p(), wi.ld, self.dec_dx[l - 1].p(), self.dec_dx[l - 1].ld, M, H, G * Hp)
                 if drop:
                     e._call(P, lib.vmmt_mul, dt, self.dec_dx[l - 1].p(), self.dec_dx[l - 1].ld, self.dec_mask[l - 1].p(),
                             self.dec_mask[l - 1].ld, self.dec_dx[l - 1].p(), self.dec_dx[l - 1].ld, M, H)
@@ -377,25 +395,25 @@ class BackwardPlan(object):
             gw = "decoder.rnn.weight_hh_l%d" % l
             grp = [] if (e.group_wgrads and dt == L.BF16) else None      # dW_hh (two pieces) and dW_ih of the layer: one grid
             if Tp > 1:
-                e._gemm(P, L.GEMM_TN, dg.p(B), dg.ld, outb.p(0, ocol), outb.ld, e.gp(gw), H, 4 * Hp, H, (Tp - 1) * B, out_f32=1, split_k=-1,
+                e._gemm(P, L.GEMM_TN, dgr.p(B), dgr.ld, outb.p(0, ocol), outb.ld, e.gp(gw), H, G * Hp, H, (Tp - 1) * B, out_f32=1, split_k=-1,
                         rmap=gmap_d, group=grp)
-            e._gemm(P, L.GEMM_TN, dg.p(0), dg.ld, self.hn[l].p(), self.hn[l].ld, e.gp(gw), H, 4 * Hp, H, B, out_f32=1, split_k=-1, rmap=gmap_d,
+            e._gemm(P, L.GEMM_TN, dgr.p(0), dgr.ld, self.hn[l].p(), self.hn[l].ld, e.gp(gw), H, G * Hp, H, B, out_f32=1, split_k=-1, rmap=gmap_d,
                     group=grp)
             gi = "decoder.rnn.weight_ih_l%d" % l
             # the bias gradient (column sums of dgates) rides in the dW_ih product, which reads all M rows of dgates anyway
-            bsum = (None, 0, e.gp("decoder.rnn.bias_ih_l%d" % l), e.gp("decoder.rnn.bias_hh_l%d" % l)) if e.lstm_db_in_gemm else None
+            bsum = (None, 0, e.gp("decoder.rnn.bias_ih_l%d" % l), e.gp("decoder.rnn.bias_hh_l%d" % l)) if db_in_gemm else None
             if l == 0:
                 if self.z_in_Xt:
                     # dW_ih [4H][E + Z] = dgates^T [emb ; z]: one product over the rows of Xt (z repeated over the steps from column Ep on);
                     # the column blocks [0, Ep) / [Ep, Ep + Z) land at columns [0, E) / [E, E + Z) of the gradient
-                    fused_b = e._gemm(P, L.GEMM_TN, dg.p(), dg.ld, self.Xt.p(), self.Xt.ld, e.gp(gi, 0, 0), E + Z, 4 * Hp, self.Ep + Z, M, out_f32=1,
+                    fused_b = e._gemm(P, L.GEMM_TN, dg.p(), dg.ld, self.Xt.p(), self.Xt.ld, e.gp(gi, 0, 0), E + Z, G * Hp, self.Ep + Z, M, out_f32=1,
                                       split_k=-1, colsum=bsum, rmap=gmap_d, cmap=(self.Ep, E), group=grp)
                     e._gemm_group(P, grp)
                 else:
-                    fused_b = e._gemm(P, L.GEMM_TN, dg.p(), dg.ld, self.Xt.p(), self.Xt.ld, e.gp(gi, 0, 0), E + Z, 4 * Hp, E, M, out_f32=1, split_k=-1,
+                    fused_b = e._gemm(P, L.GEMM_TN, dg.p(), dg.ld, self.Xt.p(), self.Xt.ld, e.gp(gi, 0, 0), E + Z, G * Hp, E, M, out_f32=1, split_k=-1,
                                       colsum=bsum, rmap=gmap_d, group=grp)
                     e._gemm_group(P, grp)
-                    e._gemm(P, L.GEMM_TN, dg.p(), dg.ld, self.zT.p(), self.zT.ld, e.gp(gi, 0, E), E + Z, 4 * Hp, Z, M, out_f32=1, split_k=-1, b_kmod=B,
+                    e._gemm(P, L.GEMM_TN, dg.p(), dg.ld, self.zT.p(), self.zT.ld, e.gp(gi, 0, E), E + Z, G * Hp, Z, M, out_f32=1, split_k=-1, b_kmod=B,
                             rmap=gmap_d)
                 we = e.sh["dec_wih_l0_e"]
                 # dX = dgates W_e, then its rows scattered into the embedding gradient (pad row dropped) -- on the SIDE stream, idle while
@@ -404,7 +422,7 @@ class BackwardPlan(object):
                 if dxt_side:
                     e._sid = SIDE
                     e._wait(P, "dec_dg%d" % l)
-                e._gemm(P, L.GEMM_NN, dg.p(), dg.ld, we.p(), we.ld, self.dXt.p(), self.dXt.ld, M, E, 4 * Hp, out_f32=1)
+                e._gemm(P, L.GEMM_NN, dg.p(), dg.ld, we.p(), we.ld, self.dXt.p(), self.dXt.ld, M, E, G * Hp, out_f32=1)
                 e._call(P, lib.vmmt_scatter_add_rows, self.dXt.p(), self.dXt.ld, self.tgt_in.data_ptr(), PAD,
                         e.gp("decoder.embeddings.make_embedding.emb_luts.0.weight"), E, M, E)
                 if spread and dxt_side and e.rows_active():
@@ -414,12 +432,14 @@ class BackwardPlan(object):
                     e._sid = AUX
             else:
                 xin = self.dec_xdrop[l - 1] if drop else self.dec_out[l - 1]
-                fused_b = e._gemm(P, L.GEMM_TN, dg.p(), dg.ld, xin.p(), xin.ld, e.gp(gi), H, 4 * Hp, H, M, out_f32=1, split_k=-1, colsum=bsum,
+                fused_b = e._gemm(P, L.GEMM_TN, dg.p(), dg.ld, xin.p(), xin.ld, e.gp(gi), H, G * Hp, H, M, out_f32=1, split_k=-1, colsum=bsum,
                                   rmap=gmap_d, group=grp)
                 e._gemm_group(P, grp)
             if not fused_b:
-                e._call(P, lib.vmmt_colsum, dt, dg.p(), dg.ld, M, 4 * Hp, Hp if Hp != H else 0, H, e.gp("decoder.rnn.bias_ih_l%d" % l),
-                        e.gp("decoder.rnn.bias_hh_l%d" % l))
+                e._call(P, lib.vmmt_colsum, dt, dg.p(), dg.ld, M, G * Hp, Hp if Hp != H else 0, H, e.gp("decoder.rnn.bias_ih_l%d" % l),
+                        None if gru else e.gp("decoder.rnn.bias_hh_l%d" % l))
+                if gru:     # db_hh from the recurrent-side matrix: its n part is sum dn r, not db_ih's sum dn
+                    e._call(P, lib.vmmt_colsum, dt, dgr.p(), dgr.ld, M, G * Hp, Hp if Hp != H else 0, H, e.gp("decoder.rnn.bias_hh_l%d" % l), None)
         if rp:
             # reparameterised gradient (H2 switched off): dL/dz = sum_t dgates_t W_z (decoder input, VI_Model1.py:99-100) + the image
             # network's gate path; it joins the KL gradient at mu / sigma, so the q(z|x) networks' backward can only start here,
@@ -427,7 +447,7 @@ class BackwardPlan(object):
             e._sid = AUX
             e._wait(P, "dec_dg0")
             dg0, wz = self.dec_dgates[0], e.sh["dec_wih_l0_z"]
-            e._gemm(P, L.GEMM_NN, dg0.p(), dg0.ld, wz.p(), wz.ld, self.dzrow.p(), self.dzrow.ld, M, Z, 4 * Hp, out_f32=1)
+            e._gemm(P, L.GEMM_NN, dg0.p(), dg0.ld, wz.p(), wz.ld, self.dzrow.p(), self.dzrow.ld, M, Z, G * Hp, out_f32=1)
             e._call(P, lib.vmmt_reparam_dz, self.dzrow.p(), self.dzrow.ld, Tp, self.dzt.p(), self.dzt.ld, self.z32.p(),
                     self.gate.data_ptr(), e.pp("inf_net_image.gate_affine_transform.weight"), self.dz.p(), B, Z)
             kl_and_q_backward()
@@ -463,6 +483,7 @@ class BackwardPlan(object):
             """dW_hh, db, dW_ih (and for layer 0 the embedding scatter) of encoder layer l from the time steps [lo, hi) of each
             direction; every product accumulates into the arena, so ranges may be issued separately"""
             dg = self.enc_dgates[l]
+            dgr = self.enc_dgh[l] if gru else dg
             wih = e.sh["enc_wih_l%d" % l]
             xin = (self.Xs if l == 0 else (self.enc_xdrop[l - 1] if drop else self.enc_out[l - 1]))
             xcols = E if l == 0 else H
@@ -472,7 +493,7 @@ class BackwardPlan(object):
                 # ... next to the embedding product, which goes out FIRST on the main stream (the grid of the group fills the chip)
                 assert all(r == (0, S) for r in ranges)
                 e._sid = MAIN
-                e._gemm(P, L.GEMM_NN, dg.p(), dg.ld, wih.p(), wih.ld, self.dXs.p(), self.dXs.ld, MS, E, dirs * 4 * Hdp, out_f32=1)
+                e._gemm(P, L.GEMM_NN, dg.p(), dg.ld, wih.p(), wih.ld, self.dXs.p(), self.dXs.ld, MS, E, dirs * G * Hdp, out_f32=1)
                 e._call(P, lib.vmmt_scatter_add_rows, self.dXs.p(), self.dXs.ld, self.src.data_ptr(), PAD,
                         e.gp("encoder.embeddings.make_embedding.emb_luts.0.weight"), E, MS, E)
                 if e.tail_norm_first and e.rows_active() and not e.dp_on():
@@ -493,27 +514,30 @@ class BackwardPlan(object):
                 if k == 0:      # h_prev[t] = out[t-1]: t in [max(lo, 1), hi)
                     t0 = max(lo, 1)
                     if hi > t0:
-                        e._gemm(P, L.GEMM_TN, dg.p(t0 * B, k * 4 * Hdp), dg.ld, self.enc_out[l].p((t0 - 1) * B, k * Hdp), self.enc_out[l].ld,
-                                e.gp(gw), Hd, 4 * Hdp, Hd, (hi - t0) * B, out_f32=1, split_k=-1, rmap=gmap_e, group=grp)
+                        e._gemm(P, L.GEMM_TN, dgr.p(t0 * B, k * G * Hdp), dgr.ld, self.enc_out[l].p((t0 - 1) * B, k * Hdp), self.enc_out[l].ld,
+                                e.gp(gw), Hd, G * Hdp, Hd, (hi - t0) * B, out_f32=1, split_k=-1, rmap=gmap_e, group=grp)
                 else:           # h_prev[t] = out[t+1]: t in [lo, min(hi, S-1))
                     t1 = min(hi, S - 1)
                     if t1 > lo:
-                        e._gemm(P, L.GEMM_TN, dg.p(lo * B, k * 4 * Hdp), dg.ld, self.enc_out[l].p((lo + 1) * B, k * Hdp), self.enc_out[l].ld,
-                                e.gp(gw), Hd, 4 * Hdp, Hd, (t1 - lo) * B, out_f32=1, split_k=-1, rmap=gmap_e, group=grp)
+                        e._gemm(P, L.GEMM_TN, dgr.p(lo * B, k * G * Hdp), dgr.ld, self.enc_out[l].p((lo + 1) * B, k * Hdp), self.enc_out[l].ld,
+                                e.gp(gw), Hd, G * Hdp, Hd, (t1 - lo) * B, out_f32=1, split_k=-1, rmap=gmap_e, group=grp)
                 alt()           # (alternating: main = the two dW_hh and the embedding product behind them, side = dW_ih + bias sums)
                 bih, bhh = e.gp("encoder.rnn.bias_ih_l%d%s" % (l, suf)), e.gp("encoder.rnn.bias_hh_l%d%s" % (l, suf))
-                fused_b = e._gemm(P, L.GEMM_TN, dg.p(lo * B, k * 4 * Hdp), dg.ld, xin.p(lo * B), xin.ld, e.gp("encoder.rnn.weight_ih_l%d%s" % (l, suf)),
-                                  xcols, 4 * Hdp, xcols, (hi - lo) * B, out_f32=1, split_k=-1, rmap=gmap_e,
-                                  colsum=(None, 0, bih, bhh) if e.lstm_db_in_gemm else None, group=grp)      # bias gradient: see the decoder's
+                fused_b = e._gemm(P, L.GEMM_TN, dg.p(lo * B, k * G * Hdp), dg.ld, xin.p(lo * B), xin.ld, e.gp("encoder.rnn.weight_ih_l%d%s" % (l, suf)),
+                                  xcols, G * Hdp, xcols, (hi - lo) * B, out_f32=1, split_k=-1, rmap=gmap_e,
+                                  colsum=(None, 0, bih, bhh) if db_in_gemm else None, group=grp)      # bias gradient: see the decoder's
                 if not fused_b:
-                    e._call(P, lib.vmmt_colsum, dt, dg.p(lo * B, k * 4 * Hdp), dg.ld, (hi - lo) * B, 4 * Hdp, Hdp if Hdp != Hd else 0, Hd, bih, bhh)
+                    e._call(P, lib.vmmt_colsum, dt, dg.p(lo * B, k * G * Hdp), dg.ld, (hi - lo) * B, G * Hdp, Hdp if Hdp != Hd else 0, Hd, bih,
+                            None if gru else bhh)
+                    if gru:
+                        e._call(P, lib.vmmt_colsum, dt, dgr.p(lo * B, k * G * Hdp), dgr.ld, (hi - lo) * B, G * Hdp, Hdp if Hdp != Hd else 0, Hd, bhh, None)
             e._gemm_group(P, grp)
             if l == 0 and grp is None:                # embedding gradient: one product over both directions, last on the main stream
                 assert all(r == (0, S) for r in ranges)
                 e._sid = MAIN
                 # (as the GEMM's own atomic epilogue the scatter costs 47 us on top of a 28 us product in isolation; in the step the two
                 #  forms measure the same -- 2.07-2.08 ms, tools/ab.py -- the row kernel is kept for its simpler access pattern)
-                e._gemm(P, L.GEMM_NN, dg.p(), dg.ld, wih.p(), wih.ld, self.dXs.p(), self.dXs.ld, MS, E, dirs * 4 * Hdp, out_f32=1)
+                e._gemm(P, L.GEMM_NN, dg.p(), dg.ld, wih.p(), wih.ld, self.dXs.p(), self.dXs.ld, MS, E, dirs * G * Hdp, out_f32=1)
                 e._call(P, lib.vmmt_scatter_add_rows, self.dXs.p(), self.dXs.ld, self.src.data_ptr(), PAD,
                         e.gp("encoder.embeddings.make_embedding.emb_luts.0.weight"), E, MS, E)
 
@@ -535,8 +559,28 @@ class BackwardPlan(object):
             elif par_top and l == Lyr - 2:
                 e._wait(P, "enc_top_dx")
             dg = self.enc_dgates[l]
-            seq = (L.LstmDirBwd * (S * dirs))()
-            for step in range(S):
+            dgr = self.enc_dgh[l] if gru else dg
+            seq = ((L.GruDirBwd if gru else L.LstmDirBwd) * (S * dirs))()
+            for step in range(S if gru else 0):
+                for k in range(dirs):
+                    t = (S - 1 - step) if k == 0 else step
+                    tn = (t + 1) if k == 0 else (t - 1)
+                    tp = (t - 1) if k == 0 else (t + 1)        # forward predecessor (h_prev; none: the zero state)
+                    a = seq[step * dirs + k]
+                    whhT = e.sh["enc_whhT_l%d_d%d" % (l, k)]
+                    if step > 0:
+                        a.dgh_next, a.ld_dgn = dgr.p(tn * B, k * G * Hdp), dgr.ld
+                    a.w_hh_t, a.ld_wt = whhT.p(), whhT.ld
+                    a.dh_above, a.ld_dha = dh_above.p(t * B, k * Hdp), dh_above.ld
+                    a.saved, a.ld_saved = self.enc_gates[l].p(t * B, k * 4 * Hdp), self.enc_gates[l].ld
+                    if 0 <= tp < S:
+                        a.h_prev, a.ld_hp = self.enc_out[l].p(tp * B, k * Hdp), self.enc_out[l].ld
+                    a.dh_carry, a.ld_dhc = self.enc_dcc[l].p(0, k * Hdp), self.enc_dcc[l].ld
+                    a.dgx_out, a.ld_dgx = dg.p(t * B, k * G * Hdp), dg.ld
+                    a.dgh_out, a.ld_dgh = dgr.p(t * B, k * G * Hdp), dgr.ld
+                    a.dh_n, a.ld_dhn = self.dec_dh0[l].p(0, k * Hdp), self.dec_dh0[l].ld     # gradient of the encoder's final h (the decoder's h0)
+                    a.t, a.inject = t, (1 if k == 0 else 2)
+            for step in range(0 if gru else S):
                 for k in range(dirs):
                     # backward visits the steps in the reverse of the forward order of that direction
                     t = (S - 1 - step) if k == 0 else step
@@ -545,7 +589,7 @@ class BackwardPlan(object):
                     a = seq[step * dirs + k]
                     whhT = e.sh["enc_whhT_l%d_d%d" % (l, k)]
                     if step > 0:
-                        a.dgates_next, a.ld_dgn = dg.p(tn * B, k * 4 * Hdp), dg.ld
+                        a.dgates_next, a.ld_dgn = dg.p(tn * B, k * G * Hdp), dg.ld
                     a.w_hh_t, a.ld_wt = whhT.p(), whhT.ld
                     a.dh_above, a.ld_dha = dh_above.p(t * B, k * Hdp), dh_above.ld
                     a.gates, a.ld_gates = self.enc_gates[l].p(t * B, k * 4 * Hdp), self.enc_gates[l].ld
@@ -553,7 +597,7 @@ class BackwardPlan(object):
                     if 0 <= tp < S:
                         a.c_prev, a.ld_cp = self.enc_c[l].p(tp * B, k * Hdp), self.enc_c[l].ld
                     a.dc_carry, a.ld_dcc = self.enc_dcc[l].p(0, k * Hdp), self.enc_dcc[l].ld
-                    a.dgates_out, a.ld_dgo = dg.p(t * B, k * 4 * Hdp), dg.ld
+                    a.dgates_out, a.ld_dgo = dg.p(t * B, k * G * Hdp), dg.ld
                     a.dh_n, a.ld_dhn = self.dec_dh0[l].p(0, k * Hdp), self.dec_dh0[l].ld
                     a.dc_n, a.ld_dcn = self.dec_dcc[l].p(0, k * Hdp), self.dec_dcc[l].ld
                     a.t = t
@@ -561,11 +605,11 @@ class BackwardPlan(object):
             # (the encoder's parameter gradients are the step's tail; cutting this recurrence into two launches so that the products of
             #  the first half of its steps run next to the second half was measured: 2.000 against 1.881 ms -- the relaunch has to wait
             #  for the product's workgroups to leave before all of its own are resident)
-            e._lstm_seq_bwd(P, seq, dirs, S, self.src_len.data_ptr(), B, Hdp)
+            (e._gru_seq_bwd if gru else e._lstm_seq_bwd)(P, seq, dirs, S, self.src_len.data_ptr(), B, Hdp)
             e._record(P, "enc_dg%d" % l)
             wih = e.sh["enc_wih_l%d" % l]
             if l > 0:
-                e._gemm(P, L.GEMM_NN, dg.p(), dg.ld, wih.p(), wih.ld, self.enc_dx[l - 1].p(), self.enc_dx[l - 1].ld, MS, H, dirs * 4 * Hdp)
+                e._gemm(P, L.GEMM_NN, dg.p(), dg.ld, wih.p(), wih.ld, self.enc_dx[l - 1].p(), self.enc_dx[l - 1].ld, MS, H, dirs * G * Hdp)
                 if drop:
                     e._call(P, lib.vmmt_mul, dt, self.enc_dx[l - 1].p(), self.enc_dx[l - 1].ld, self.enc_mask[l - 1].p(),
                             self.enc_mask[l - 1].ld, self.enc_dx[l - 1].p(), self.enc_dx[l - 1].ld, MS, H)

@@ -544,7 +544,7 @@ class Engine(StepAPI):
         self.sh = {}
         self.pack_calls = []
 
-        def shadow(key, rows, cols, src, c0=0, ncols=None, transpose=False, dtype=None, src2=None, row_off=0, col_off=0, gate=None):
+        def shadow(key, rows, cols, src, c0=0, ncols=None, transpose=False, dtype=None, src2=None, row_off=0, col_off=0, gate=None, src2_blocks=None):
             """one compute copy (or one piece of it).  (row_off, col_off): position of the piece in the shadow as stored, i.e. AFTER the
             transpose.  gate = (h, hp), h != hp: the source's 4h rows (a bias: its 4h entries) are nn.LSTM's gate blocks i, f, g, o; block
             g lands at g * hp of the shadow (Dims.hp): one pack descriptor per block"""
@@ -558,8 +558,10 @@ class Engine(StepAPI):
             if key not in self.sh:
                 self.sh[key] = Buf(rows, cols, dt, dev)
             b = self.sh[key]
-            blocks = [(0, 0)] if (gate is None or gate[0] == gate[1]) else [(g * gate[0], g * gate[1]) for g in range(4)]
-            for s0, d0 in blocks:
+            # (src2_blocks = n: only the first n gate blocks take src2 -- the GRU's folded bias row is b_ih plus b_hh's r and z parts)
+            blocks = ([(0, 0)] if (gate is None or (gate[0] == gate[1] and src2_blocks is None))
+                      else [(g * gate[0], g * gate[1]) for g in range(d.gates)])
+            for gi_, (s0, d0) in enumerate(blocks):
                 if len(blocks) > 1:
                     if two_d:
                         R = gate[0]
@@ -570,31 +572,36 @@ class Engine(StepAPI):
                     s2 = self.pp(src2, s0, c0) if src2 else None
                     dst = b.p(row_off + d0, col_off) if not transpose else b.p(row_off, col_off + d0)
                 else:           # a bias vector [4h] packed as one row
-                    sp = self.pp(src, 0, s0)
-                    s2 = self.pp(src2, 0, s0) if src2 else None
+                    sp = self.pp(src, 0, s0 + c0)
+                    s2 = self.pp(src2, 0, s0) if (src2 and (src2_blocks is None or gi_ < src2_blocks)) else None
                     dst = b.p(row_off, col_off + d0)
                 self.pack_calls.append((code, sp, s2, ld_src, dst, b.ld, R, Cc, 1 if transpose else 0))
 
+        G, fold = d.gates, (2 if d.rnn == "GRU" else None)
         ge, gd = (d.hd, d.hdp), (d.hid, d.hp)       # gate blocks of the encoder's directions / of the decoder as stored -> as computed
         for l in range(d.layers):
             i = d.emb if l == 0 else d.hid
             for k, suf in enumerate([""] + (["_reverse"] if d.brnn else [])):
                 # concatenated over directions: rows k*4Hd ..
-                shadow("enc_wih_l%d" % l, d.dirs * 4 * d.hdp, i, "encoder.rnn.weight_ih_l%d%s" % (l, suf), row_off=k * 4 * d.hdp, gate=ge)
-                shadow("enc_b_l%d" % l, 1, d.dirs * 4 * d.hdp, "encoder.rnn.bias_ih_l%d%s" % (l, suf), dtype=torch.float32,
-                       src2="encoder.rnn.bias_hh_l%d%s" % (l, suf), col_off=k * 4 * d.hdp, gate=ge)
-                shadow("enc_whh_l%d_d%d" % (l, k), 4 * d.hdp, d.hd, "encoder.rnn.weight_hh_l%d%s" % (l, suf), gate=ge)
-                shadow("enc_whhT_l%d_d%d" % (l, k), d.hd, 4 * d.hdp, "encoder.rnn.weight_hh_l%d%s" % (l, suf), transpose=True, gate=ge)
+                shadow("enc_wih_l%d" % l, d.dirs * G * d.hdp, i, "encoder.rnn.weight_ih_l%d%s" % (l, suf), row_off=k * G * d.hdp, gate=ge)
+                shadow("enc_b_l%d" % l, 1, d.dirs * G * d.hdp, "encoder.rnn.bias_ih_l%d%s" % (l, suf), dtype=torch.float32,
+                       src2="encoder.rnn.bias_hh_l%d%s" % (l, suf), col_off=k * G * d.hdp, gate=ge, src2_blocks=fold)
+                if d.rnn == "GRU":      # b_hn sits inside r * (.): an operand of the step, f32, zeros in padded lanes
+                    shadow("enc_bhn_l%d_d%d" % (l, k), 1, d.hdp, "encoder.rnn.bias_hh_l%d%s" % (l, suf), dtype=torch.float32, c0=2 * d.hd, ncols=d.hd)
+                shadow("enc_whh_l%d_d%d" % (l, k), G * d.hdp, d.hd, "encoder.rnn.weight_hh_l%d%s" % (l, suf), gate=ge)
+                shadow("enc_whhT_l%d_d%d" % (l, k), d.hd, G * d.hdp, "encoder.rnn.weight_hh_l%d%s" % (l, suf), transpose=True, gate=ge)
         for l in range(d.layers):
             if l == 0:
-                shadow("dec_wih_l0_e", 4 * d.hp, d.emb, "decoder.rnn.weight_ih_l0", c0=0, ncols=d.emb, gate=gd)
-                shadow("dec_wih_l0_z", 4 * d.hp, d.z, "decoder.rnn.weight_ih_l0", c0=d.emb, ncols=d.z, gate=gd)
+                shadow("dec_wih_l0_e", G * d.hp, d.emb, "decoder.rnn.weight_ih_l0", c0=0, ncols=d.emb, gate=gd)
+                shadow("dec_wih_l0_z", G * d.hp, d.z, "decoder.rnn.weight_ih_l0", c0=d.emb, ncols=d.z, gate=gd)
             else:
-                shadow("dec_wih_l%d" % l, 4 * d.hp, d.hid, "decoder.rnn.weight_ih_l%d" % l, gate=gd)
-            shadow("dec_b_l%d" % l, 1, 4 * d.hp, "decoder.rnn.bias_ih_l%d" % l, dtype=torch.float32,
-                   src2="decoder.rnn.bias_hh_l%d" % l, gate=gd)
-            shadow("dec_whh_l%d" % l, 4 * d.hp, d.hid, "decoder.rnn.weight_hh_l%d" % l, gate=gd)
-            shadow("dec_whhT_l%d" % l, d.hid, 4 * d.hp, "decoder.rnn.weight_hh_l%d" % l, transpose=True, gate=gd)
+                shadow("dec_wih_l%d" % l, G * d.hp, d.hid, "decoder.rnn.weight_ih_l%d" % l, gate=gd)
+            shadow("dec_b_l%d" % l, 1, G * d.hp, "decoder.rnn.bias_ih_l%d" % l, dtype=torch.float32,
+                   src2="decoder.rnn.bias_hh_l%d" % l, gate=gd, src2_blocks=fold)
+            if d.rnn == "GRU":
+                shadow("dec_bhn_l%d" % l, 1, d.hp, "decoder.rnn.bias_hh_l%d" % l, dtype=torch.float32, c0=2 * d.hid, ncols=d.hid)
+            shadow("dec_whh_l%d" % l, G * d.hp, d.hid, "decoder.rnn.weight_hh_l%d" % l, gate=gd)
+            shadow("dec_whhT_l%d" % l, d.hid, G * d.hp, "decoder.rnn.weight_hh_l%d" % l, transpose=True, gate=gd)
         if d.attn == "general":
             shadow("wa", d.hid, d.hid, "decoder.attn.linear_in.weight")
         elif d.attn == "mlp":                # W_q takes linear_in's place (both multiply the decoder output); W_c multiplies the memory
@@ -808,6 +815,17 @@ class Engine(StepAPI):
             self.seq_syncs.append(sync)
         else:
             plan.append((self.lib.vmmt_lstm_chain_fwd, (self.dt, ndir, nsteps, arr, lens_ptr, B, H), "vmmt_lstm_chain_fwd", arr, self._sid))
+
+    def _gru_seq_fwd(self, plan, arr, ndir, nsteps, lens_ptr, B, H):
+        """plan entry: a whole GRU forward recurrence, one launch per step (csrc/gru.hip; there is no persistent GRU)"""
+        plan.append((self.lib.vmmt_gru_chain_fwd, (self.dt, ndir, nsteps, arr, lens_ptr, B, H), "vmmt_gru_chain_fwd", arr, self._sid))
+
+    def _gru_seq_bwd(self, plan, arr, ndir, nsteps, lens_ptr, B, H, with_dh0=0):
+        """... and the backward one (with_dh0: `arr` holds one more step, the mode-1 descriptor of the initial state's gradient)"""
+        plan.append((self.lib.vmmt_gru_chain_bwd, (self.dt, ndir, nsteps, arr, lens_ptr, B, H, 0), "vmmt_gru_chain_bwd", arr, self._sid))
+        if with_dh0:
+            last = C.cast(C.byref(arr, nsteps * ndir * C.sizeof(L.GruDirBwd)), C.POINTER(L.GruDirBwd))
+            plan.append((self.lib.vmmt_gru_step_bwd, (self.dt, ndir, last, lens_ptr, B, H, 1), "vmmt_gru_step_bwd", arr, self._sid))
 
     def _lstm_seq_bwd(self, plan, arr, ndir, nsteps, lens_ptr, B, H, with_dh0=0):
         """plan entry: a whole backward recurrence (the mode-0 steps; with_dh0: `arr` ends with one mode-1 step, the gradient of

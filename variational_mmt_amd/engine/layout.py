@@ -16,11 +16,16 @@ def _ru(x, m):
 
 
 class Dims(object):
-    def __init__(self, vs, vt, emb=500, hid=500, z=500, img=2048, layers=2, brnn=False, dropout=0.0, conditional=False, attn="general"):
+    def __init__(self, vs, vt, emb=500, hid=500, z=500, img=2048, layers=2, brnn=False, dropout=0.0, conditional=False, attn="general", rnn="LSTM"):
         assert attn in ("general", "dot", "mlp"), attn          # -global_attention (onmt/modules/GlobalAttention.py:70-78)
         if attn != "general" and conditional:
             raise NotImplementedError("-global_attention %s with --conditional is not built (the conditional plans keep `general`)" % attn)
         self.attn = attn
+        assert rnn in ("LSTM", "GRU"), rnn                      # -rnn_type (onmt/Models.py:124-129, onmt/VI_Model1.py:137-152); SRU is refused upstream
+        if rnn == "GRU" and conditional:
+            raise NotImplementedError("-rnn_type GRU with --conditional is not built (the conditional plans keep the LSTM)")
+        self.rnn = rnn
+        self.gates = 4 if rnn == "LSTM" else 3                  # gate blocks of the recurrent parameters: i,f,g,o / r,z,n
         self.vs, self.vt, self.emb, self.hid, self.z, self.img = vs, vt, emb, hid, z, img
         self.layers, self.brnn, self.dropout = layers, bool(brnn), float(dropout)
         self.conditional = bool(conditional)       # --conditional prior (ModelConstructor.py:435-460)
@@ -51,6 +56,7 @@ class Dims(object):
         """name -> shape, in ARENA order (reverse of backward completion is not needed: order == completion)."""
         d = self
         s = []
+        G = d.gates
         s += [("generator.0.weight", (d.vt, d.hid)), ("generator.0.bias", (d.vt,))]
         s += [("decoder.attn.linear_out.weight", (d.hid, 2 * d.hid))]       # first of its segment (Engine: seg_starts)
         if d.attn == "general":
@@ -61,16 +67,16 @@ class Dims(object):
                   ("decoder.attn.v.weight", (1, d.hid))]
         for l in reversed(range(d.layers)):
             i = d.emb + d.z if l == 0 else d.hid
-            s += [("decoder.rnn.weight_ih_l%d" % l, (4 * d.hid, i)), ("decoder.rnn.weight_hh_l%d" % l, (4 * d.hid, d.hid)),
-                  ("decoder.rnn.bias_ih_l%d" % l, (4 * d.hid,)), ("decoder.rnn.bias_hh_l%d" % l, (4 * d.hid,))]
+            s += [("decoder.rnn.weight_ih_l%d" % l, (G * d.hid, i)), ("decoder.rnn.weight_hh_l%d" % l, (G * d.hid, d.hid)),
+                  ("decoder.rnn.bias_ih_l%d" % l, (G * d.hid,)), ("decoder.rnn.bias_hh_l%d" % l, (G * d.hid,))]
         s += [("decoder.embeddings.make_embedding.emb_luts.0.weight", (d.vt, d.emb))]
         for l in reversed(range(d.layers)):
             i = d.emb if l == 0 else d.hid
             for suf in ([""] + (["_reverse"] if d.brnn else [])):
-                s += [("encoder.rnn.weight_ih_l%d%s" % (l, suf), (4 * d.hd, i)),
-                      ("encoder.rnn.weight_hh_l%d%s" % (l, suf), (4 * d.hd, d.hd)),
-                      ("encoder.rnn.bias_ih_l%d%s" % (l, suf), (4 * d.hd,)),
-                      ("encoder.rnn.bias_hh_l%d%s" % (l, suf), (4 * d.hd,))]
+                s += [("encoder.rnn.weight_ih_l%d%s" % (l, suf), (G * d.hd, i)),
+                      ("encoder.rnn.weight_hh_l%d%s" % (l, suf), (G * d.hd, d.hd)),
+                      ("encoder.rnn.bias_ih_l%d%s" % (l, suf), (G * d.hd,)),
+                      ("encoder.rnn.bias_hh_l%d%s" % (l, suf), (G * d.hd,))]
         s += [("encoder.embeddings.make_embedding.emb_luts.0.weight", (d.vs, d.emb))]
         if d.conditional:
             for br in ("location", "scale"):       # p(z|x)

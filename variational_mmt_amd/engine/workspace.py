@@ -20,6 +20,7 @@ class Workspace(BackwardPlan, ConditionalPlans):
         d, T, dev = eng.d, eng.T, eng.dev
         f32, i64 = torch.float32, torch.int64
         H, Hd, E, Z, D, V, Lyr, dirs = d.hid, d.hd, d.emb, d.z, d.img, d.vt, d.layers, d.dirs
+        G, gru = d.gates, d.rnn == "GRU"
         Hp, Hdp = d.hp, d.hdp         # hidden sizes as computed (Dims.hp): gate g of a 4H vector at column g * Hp; [c ; r] halves at 0 / Hp
         M, MS = Tp * B, S * B
         self.M, self.MS = M, MS
@@ -36,7 +37,7 @@ class Workspace(BackwardPlan, ConditionalPlans):
         self.kl_global = torch.zeros(1, dtype=f32, device=dev)
         # encoder
         self.Xs = nb(MS, E)
-        self.enc_gx = [nb(MS, dirs * 4 * Hdp, f32) for _ in range(Lyr)]
+        self.enc_gx = [nb(MS, dirs * G * Hdp, f32) for _ in range(Lyr)]
         self.enc_gates = [nb(MS, dirs * 4 * Hdp) for _ in range(Lyr)]
         self.enc_c = [nb(MS, H, f32) for _ in range(Lyr)]
         self.enc_out = [nb(MS, H) for _ in range(Lyr)]
@@ -61,8 +62,8 @@ class Workspace(BackwardPlan, ConditionalPlans):
         self.z_in_Xt = bool(Z <= E)
         self.Xt = nb(M, E, ld=self.Ep + _ru(Z, KPAD)) if self.z_in_Xt else nb(M, E)
         self.zrep_ids = (torch.arange(M, dtype=i64) % B).to(dev) if self.z_in_Xt else None
-        self.zx = nb(B, 4 * Hp, f32)
-        self.dec_gx = [nb(M, 4 * Hp, f32) for _ in range(Lyr)]
+        self.zx = nb(B, G * Hp, f32)
+        self.dec_gx = [nb(M, G * Hp, f32) for _ in range(Lyr)]
         self.dec_gates = [nb(M, 4 * Hp) for _ in range(Lyr)]
         self.dec_c = [nb(M, H, f32) for _ in range(Lyr)]
         self.dec_out = [nb(M, H) for _ in range(Lyr - 1)]
@@ -142,11 +143,14 @@ class Workspace(BackwardPlan, ConditionalPlans):
         self.dQ = nb(M, H)
         self.dctx = nb(MS, H)
         self.dR = nb(M, H)
-        self.dec_dgates = [nb(M, 4 * Hp) for _ in range(Lyr)]
+        self.dec_dgates = [nb(M, G * Hp) for _ in range(Lyr)]
         self.dec_dcc = [nb(B, H, f32) for _ in range(Lyr)]
         self.dec_dh0 = [nb(B, H, f32) for _ in range(Lyr)]
         self.dec_dx = [nb(M, H) for _ in range(Lyr - 1)]
-        self.enc_dgates = [nb(MS, dirs * 4 * Hdp) for _ in range(Lyr)]
+        self.enc_dgates = [nb(MS, dirs * G * Hdp) for _ in range(Lyr)]
+        # GRU: the recurrent-side gate gradients [dr, dz, dn r] next to the input-side ones [dr, dz, dn] (csrc/gru.hip)
+        self.enc_dgh = [nb(MS, dirs * G * Hdp) for _ in range(Lyr)] if gru else None
+        self.dec_dgh = [nb(M, G * Hp) for _ in range(Lyr)] if gru else None
         self.enc_dcc = [nb(B, H, f32) for _ in range(Lyr)]
         self.enc_dx = [nb(MS, H) for _ in range(Lyr - 1)]
         self.q_dmu = nb(B, Z)
@@ -172,7 +176,7 @@ class Workspace(BackwardPlan, ConditionalPlans):
         e, d, lib = self.e, self.e.d, self.e.lib
         B, S, Tp, M, MS = self.B, self.S, self.Tp, self.M, self.MS
         H, Hd, E, Z, D, V, Lyr, dirs = d.hid, d.hd, d.emb, d.z, d.img, d.vt, d.layers, d.dirs
-        Hp, Hdp = d.hp, d.hdp
+        Hp, Hdp, G = d.hp, d.hdp, d.gates
         dt = e.dt
         P = []
         drop = training and d.dropout > 0
@@ -194,10 +198,10 @@ class Workspace(BackwardPlan, ConditionalPlans):
         def enc_gx0():
             wih, bsum = e.sh["enc_wih_l0"], e.sh["enc_b_l0"]
             if emb_tab is not None:
-                e._gemm(P, L.GEMM_NT, emb_tab.p(), emb_tab.ld, wih.p(), wih.ld, self.enc_gx[0].p(), self.enc_gx[0].ld, MS, dirs * 4 * Hdp,
+                e._gemm(P, L.GEMM_NT, emb_tab.p(), emb_tab.ld, wih.p(), wih.ld, self.enc_gx[0].p(), self.enc_gx[0].ld, MS, dirs * G * Hdp,
                         E, addend=bsum.p(), ld_add=bsum.ld, add_rows=1, out_f32=1, a_row_ids=self.src.data_ptr())
             else:
-                e._gemm(P, L.GEMM_NT, self.Xs.p(), self.Xs.ld, wih.p(), wih.ld, self.enc_gx[0].p(), self.enc_gx[0].ld, MS, dirs * 4 * Hdp,
+                e._gemm(P, L.GEMM_NT, self.Xs.p(), self.Xs.ld, wih.p(), wih.ld, self.enc_gx[0].p(), self.enc_gx[0].ld, MS, dirs * G * Hdp,
                         E, addend=bsum.p(), ld_add=bsum.ld, add_rows=1, out_f32=1)
         if early_head:
             e._row_mark_entries(P, 0, self.src.data_ptr(), MS, with_shadow=emb_tab is not None)
@@ -232,7 +236,7 @@ class Workspace(BackwardPlan, ConditionalPlans):
             e._call(P, lib.vmmt_gather_rows, dt, e.pp("decoder.embeddings.make_embedding.emb_luts.0.weight"), E,
                     self.tgt_in.data_ptr(), self.Xt.p(), self.Xt.ld, M, E)
             we = e.sh["dec_wih_l0_e"]
-            e._gemm(P, L.GEMM_NT, self.Xt.p(), self.Xt.ld, we.p(), we.ld, self.dec_gx[0].p(), self.dec_gx[0].ld, M, 4 * Hp, E, out_f32=1)
+            e._gemm(P, L.GEMM_NT, self.Xt.p(), self.Xt.ld, we.p(), we.ld, self.dec_gx[0].p(), self.dec_gx[0].ld, M, G * Hp, E, out_f32=1)
             e._record(P, "dec_gx")
         # ---- side stream, underneath the encoder: zero the gradient arena (every gradient writer of the backward plan
         #      runs on the side stream), target embeddings and the time-parallel part of the decoder input projection
@@ -320,12 +324,26 @@ class Workspace(BackwardPlan, ConditionalPlans):
                 if not early_head:
                     enc_gx0()
             else:
-                e._gemm(P, L.GEMM_NT, x.p(), x.ld, wih.p(), wih.ld, self.enc_gx[l].p(), self.enc_gx[l].ld, MS, dirs * 4 * Hdp,
+                e._gemm(P, L.GEMM_NT, x.p(), x.ld, wih.p(), wih.ld, self.enc_gx[l].p(), self.enc_gx[l].ld, MS, dirs * G * Hdp,
                         xcols, addend=bsum.p(), ld_add=bsum.ld, add_rows=1, out_f32=1)
-            seq = (L.LstmDirFwd * (S * dirs))()                 # the whole recurrence: step-major, then direction
+            gru = d.rnn == "GRU"
+            seq = ((L.GruDirFwd if gru else L.LstmDirFwd) * (S * dirs))()                 # the whole recurrence: step-major, then direction
             if not hasattr(self, "hzero"):
                 self.hzero = Buf(B, H, e.T, e.dev)              # first step: h_prev reads zeros
-            for step in range(S):
+            for step in range(S if gru else 0):
+                for k in range(dirs):                            # GRU: no cell state; r, z, n, hn saved in the LSTM's gate buffer
+                    t = step if k == 0 else S - 1 - step
+                    tp = (t - 1) if k == 0 else (t + 1)
+                    whh, a = e.sh["enc_whh_l%d_d%d" % (l, k)], seq[step * dirs + k]
+                    a.h_prev, a.ld_hprev = (self.hzero.p(0, k * Hdp), self.hzero.ld) if step == 0 else (self.enc_out[l].p(tp * B, k * Hdp), self.enc_out[l].ld)
+                    a.w_hh, a.ld_w = whh.p(), whh.ld
+                    a.gx, a.ld_gx = self.enc_gx[l].p(t * B, k * G * Hdp), self.enc_gx[l].ld
+                    a.b_hn = e.sh["enc_bhn_l%d_d%d" % (l, k)].p()
+                    a.saved, a.ld_saved = self.enc_gates[l].p(t * B, k * 4 * Hdp), self.enc_gates[l].ld
+                    a.h_out, a.ld_h = self.enc_out[l].p(t * B, k * Hdp), self.enc_out[l].ld
+                    a.h_n, a.ld_hn = self.hn[l].p(0, k * Hdp), self.hn[l].ld
+                    a.t, a.capture = t, (1 if k == 0 else 2)
+            for step in range(0 if gru else S):
                 for k in range(dirs):
                     t = step if k == 0 else S - 1 - step
                     tp = (t - 1) if k == 0 else (t + 1)
@@ -337,7 +355,7 @@ class Workspace(BackwardPlan, ConditionalPlans):
                     a.c_prev = None if first else self.enc_c[l].p(tp * B, k * Hdp)
                     a.ld_cprev = self.enc_c[l].ld
                     a.w_hh, a.ld_w = whh.p(), whh.ld
-                    a.gx, a.ld_gx = self.enc_gx[l].p(t * B, k * 4 * Hdp), self.enc_gx[l].ld
+                    a.gx, a.ld_gx = self.enc_gx[l].p(t * B, k * G * Hdp), self.enc_gx[l].ld
                     a.gates, a.ld_gates = self.enc_gates[l].p(t * B, k * 4 * Hdp), self.enc_gates[l].ld
                     a.c_out, a.ld_c = self.enc_c[l].p(t * B, k * Hdp), self.enc_c[l].ld
                     a.h_out, a.ld_h = self.enc_out[l].p(t * B, k * Hdp), self.enc_out[l].ld
@@ -347,7 +365,7 @@ class Workspace(BackwardPlan, ConditionalPlans):
                     a.capture = 1 if k == 0 else 2
                     if first:
                         a.h_prev, a.ld_hprev = self.hzero.p(0, k * Hdp), self.hzero.ld
-            e._lstm_seq_fwd(P, seq, dirs, S, self.src_len.data_ptr(), B, Hdp)
+            (e._gru_seq_fwd if gru else e._lstm_seq_fwd)(P, seq, dirs, S, self.src_len.data_ptr(), B, Hdp)
             x, xcols = self.enc_out[l], H
             if l < Lyr - 1 and drop:
                 e._call(P, lib.vmmt_mul, dt, self.enc_out[l].p(), self.enc_out[l].ld, self.enc_mask[l].p(), self.enc_mask[l].ld,
@@ -425,7 +443,7 @@ class Workspace(BackwardPlan, ConditionalPlans):
         # a6 decoder: gx[t] = emb(y_t) W_e^T (side stream, above) ; zx = z W_z^T + b is added inside the step kernel
         e._wait(P, "opt_side_done")      # decoder / attention / generator parameters + shadows of the previous update
         wz, bsum = e.sh["dec_wih_l0_z"], e.sh["dec_b_l0"]
-        e._gemm(P, L.GEMM_NT, self.zT.p(), self.zT.ld, wz.p(), wz.ld, self.zx.p(), self.zx.ld, B, 4 * Hp, Z,
+        e._gemm(P, L.GEMM_NT, self.zT.p(), self.zT.ld, wz.p(), wz.ld, self.zx.p(), self.zx.ld, B, G * Hp, Z,
                 addend=bsum.p(), ld_add=bsum.ld, add_rows=1, out_f32=1)
         x, xcols = self.Xt, E
         for l in range(Lyr):
@@ -433,13 +451,24 @@ class Workspace(BackwardPlan, ConditionalPlans):
                 e._wait(P, "dec_gx")
             else:
                 wi, bs = e.sh["dec_wih_l%d" % l], e.sh["dec_b_l%d" % l]
-                e._gemm(P, L.GEMM_NT, x.p(), x.ld, wi.p(), wi.ld, self.dec_gx[l].p(), self.dec_gx[l].ld, M, 4 * Hp, H,
+                e._gemm(P, L.GEMM_NT, x.p(), x.ld, wi.p(), wi.ld, self.dec_gx[l].p(), self.dec_gx[l].ld, M, G * Hp, H,
                         addend=bs.p(), ld_add=bs.ld, add_rows=1, out_f32=1)
             last = l == Lyr - 1
             outb, ocol = (self.cat, Hp) if last else (self.dec_out[l], 0)
             whh = e.sh["dec_whh_l%d" % l]
-            seq = (L.LstmDirFwd * Tp)()
-            for t in range(Tp):
+            seq = ((L.GruDirFwd if gru else L.LstmDirFwd) * Tp)()
+            for t in range(Tp if gru else 0):                   # GRU: the initial state is the encoder's final h alone (Models.py:1167-1174)
+                a = seq[t]
+                a.h_prev, a.ld_hprev = (self.hn[l].p(), self.hn[l].ld) if t == 0 else (outb.p((t - 1) * B, ocol), outb.ld)
+                a.w_hh, a.ld_w = whh.p(), whh.ld
+                a.gx, a.ld_gx = self.dec_gx[l].p(t * B), self.dec_gx[l].ld
+                if l == 0:
+                    a.gx2, a.ld_gx2 = self.zx.p(), self.zx.ld
+                a.b_hn = e.sh["dec_bhn_l%d" % l].p()
+                a.saved, a.ld_saved = self.dec_gates[l].p(t * B), self.dec_gates[l].ld
+                a.h_out, a.ld_h = outb.p(t * B, ocol), outb.ld
+                a.h_n, a.t, a.capture = None, t, 0
+            for t in range(0 if gru else Tp):
                 a = seq[t]
                 if t == 0:
                     a.h_prev, a.ld_hprev = self.hn[l].p(), self.hn[l].ld
@@ -455,7 +484,7 @@ class Workspace(BackwardPlan, ConditionalPlans):
                 a.c_out, a.ld_c = self.dec_c[l].p(t * B), self.dec_c[l].ld
                 a.h_out, a.ld_h = outb.p(t * B, ocol), outb.ld
                 a.h_n, a.c_n, a.t, a.capture = None, None, t, 0
-            e._lstm_seq_fwd(P, seq, 1, Tp, None, B, Hp)
+            (e._gru_seq_fwd if gru else e._lstm_seq_fwd)(P, seq, 1, Tp, None, B, Hp)
             if not last:
                 x, xcols = self.dec_out[l], H
                 if drop:

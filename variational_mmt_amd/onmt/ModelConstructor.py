@@ -19,9 +19,9 @@ def make_vi_model_mmt(model_opt, fields, gpu, checkpoint=None):
     model_opt.global_image_features_dim = feat
     if not gpu:
         raise RuntimeError("variational_mmt_amd needs -gpuid (MI355X); there is no CPU path")
-    for flag, ok in (("rnn_type", "LSTM"),):
-        if getattr(model_opt, flag, ok) != ok:
-            raise NotImplementedError("%s=%s is outside the hot path (reference run scripts use %s)" % (flag, getattr(model_opt, flag), ok))
+    rnn_type = getattr(model_opt, "rnn_type", "LSTM")       # Models.py:124-129, VI_Model1.py:137-152: getattr(nn, rnn_type)
+    if rnn_type not in ("LSTM", "GRU"):
+        raise NotImplementedError("rnn_type=%s is outside the hot path (LSTM and GRU are built)" % rnn_type)
     for flag in ("copy_attn", "coverage_attn", "share_embeddings", "share_decoder_embeddings", "non_shared_inference_network",
                  "use_local_image_features", "two_step_image_prediction"):
         if getattr(model_opt, flag, False):
@@ -35,7 +35,7 @@ def make_vi_model_mmt(model_opt, fields, gpu, checkpoint=None):
     dims = Dims(vs=len(fields["src"].vocab), vt=len(fields["tgt"].vocab), emb=model_opt.src_word_vec_size,
                 hid=model_opt.rnn_size, z=model_opt.z_latent_dim, img=feat, layers=model_opt.enc_layers, brnn=brnn,
                 dropout=model_opt.dropout, conditional=bool(getattr(model_opt, "conditional", False)),
-                attn=getattr(model_opt, "global_attention", "general"))
+                attn=getattr(model_opt, "global_attention", "general"), rnn=rnn_type)
     dtype = getattr(model_opt, "compute_dtype", "bf16")
     dev = "cuda:%d" % (model_opt.gpuid[0] if getattr(model_opt, "gpuid", None) else torch.cuda.current_device())
     model = NMTVIModel(dims, dtype=dtype, device=dev, param_init=(0.0 if checkpoint is not None else model_opt.param_init),

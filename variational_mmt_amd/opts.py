@@ -85,7 +85,7 @@ _MODEL = [
         ("-rnn_size", int, 500, dict(help="LSTM hidden size (computed padded to a multiple of 32 on the MI355X path)")),
         ("-cnn_kernel_width", int, 3, dict(help="kernel width of the cnn encoder / decoder")),
         ("-input_feed", int, 1, dict(help="input feeding (the VI_Model1 decoder does not use it)")),
-        ("-rnn_type", CheckSRU, "LSTM", dict(type=str, choices=["LSTM", "GRU", "SRU"], help="gate type; LSTM on the MI355X path")),
+        ("-rnn_type", CheckSRU, "LSTM", dict(type=str, choices=["LSTM", "GRU", "SRU"], help="gate type; LSTM and GRU run on the MI355X path (GRU not with --conditional), SRU is refused")),
         ("-brnn", "dead", None, dict(help="Use `encoder_type`.")),
         ("-brnn_merge", None, "concat", dict(choices=["concat", "sum"], help="how a brnn's directions are merged")),
         ("-context_gate", str, None, dict(choices=["source", "target", "both"], help="context gate (not on the MI355X path)")),
