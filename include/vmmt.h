@@ -621,6 +621,29 @@ int vmmt_adam_rows_step(float* p, float* g, float* m, float* v, int R, int C, co
 int vmmt_sumsq_rows(const float* g, int R, int C, const int32_t* flags, const int32_t* hist, float* rowsq, float* scratch, int slot,
                     void* stream);
 
+/* ---- optimiser: -optim sgd | adagrad | adadelta (onmt/Optim.py:56-67: torch.optim.SGD / Adagrad / Adadelta(params, lr=lr)) ---------
+ * The same fused clip + update as vmmt_adam_step_ranges / vmmt_adam_rows_step, minus the betas and the bias-correction step, for the
+ * three other methods of the reference at torch's defaults: momentum 0, weight decay 0; Adagrad lr_decay 0, eps 1e-10 (the caller fills
+ * `sum` with adagrad_accum); Adadelta rho 0.9, eps 1e-6, lr on the delta.  State arrays (the arena's flat_m / flat_v):
+ *   method     s1            s2
+ *   SGD        unused        unused      (may be NULL)
+ *   ADAGRAD    sum           unused
+ *   ADADELTA   square_avg    acc_delta
+ * Only the arrays a method uses are read or written.  Clip, grad_scale, max_blocks, the hole, the shadow and `skip` are Adam's.
+ *   vmmt_optim_rows_step  SGD and ADAGRAD only: a zero-gradient step of these is the identity, so only the flagged rows are updated (g is
+ *                         read for them alone).  The step is recorded in the ring as one with nothing to replay -- entry (lr, 0, 0, step),
+ *                         hist[0] = step -- and last[r] = step for the flagged rows and the rows r % roll == step % roll, whose data is
+ *                         not touched: vmmt_rows_mark / _catchup / vmmt_sumsq_rows work on unchanged (a catch-up finds nothing to replay,
+ *                         clears the gradient rows and writes the bf16 copy).  A skipped step leaves `last` alone as well. */
+#define VMMT_OPTIM_SGD 0
+#define VMMT_OPTIM_ADAGRAD 1
+#define VMMT_OPTIM_ADADELTA 2
+int vmmt_optim_step_ranges(int method, float* p, const float* g, float* s1, float* s2, int64_t span, int64_t hole_lo, int64_t hole_n, float lr,
+                           float max_norm, const float* sumsq, float grad_scale, int max_blocks, void* shadow_bf16, int64_t shadow_lo,
+                           int64_t shadow_n, const int32_t* skip, void* stream);
+int vmmt_optim_rows_step(int method, float* p, const float* g, float* s1, int R, int C, const int32_t* flags, int32_t* last, int32_t* hist, float lr,
+                         int step, int roll, float max_norm, const float* sumsq, float grad_scale, const int32_t* skip, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

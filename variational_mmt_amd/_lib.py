@@ -22,6 +22,8 @@ SEQ_GUARD_WORD = 4 + 2 * 256                                        # vmmt.h: VM
 SUMSQ_SCRATCH = 2 * SUMSQ_SLOTS + SUMSQ_SLOTS * SUMSQ_MAXBLOCKS      # vmmt.h: VMMT_SUMSQ_SCRATCH
 LAZY_HIST = 128                                                     # vmmt.h: VMMT_LAZY_HIST
 LAZY_HIST_WORDS = 4 + 4 * LAZY_HIST                                  # vmmt.h: VMMT_LAZY_HIST_WORDS
+OPTIM_SGD, OPTIM_ADAGRAD, OPTIM_ADADELTA = 0, 1, 2                  # vmmt.h: VMMT_OPTIM_* (Adam has entry points of its own)
+OPTIM_METHODS = {"sgd": OPTIM_SGD, "adagrad": OPTIM_ADAGRAD, "adadelta": OPTIM_ADADELTA}
 
 vp, i64, i32, f32, u64 = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_uint64
 
@@ -162,6 +164,8 @@ _SIGS = {
     "vmmt_rows_catchup_shadow": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, f32, f32, f32, vp, i64, vp]),
     "vmmt_adam_rows_step": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, f32, f32, f32, f32, i32, i32, f32, vp, f32, vp, vp]),
     "vmmt_sumsq_rows": (i32, [vp, i32, i32, vp, vp, vp, vp, i32, vp]),
+    "vmmt_optim_step_ranges": (i32, [i32, vp, vp, vp, vp, i64, i64, i64, f32, f32, vp, f32, i32, vp, i64, i64, vp, vp]),
+    "vmmt_optim_rows_step": (i32, [i32, vp, vp, vp, i32, i32, vp, vp, vp, f32, i32, i32, f32, vp, f32, vp, vp]),
 }
 
 EXPORTS = sorted(_SIGS)

@@ -170,8 +170,10 @@ class GradSync(object):
                 self._direct_up()
             elif self.backend == "nccl":
                 self._log("step collectives", "torch.distributed", "direct RCCL is opt-in: VMMT_DP_DIRECT=1" if not want else "VMMT_DP_NATIVE=0 / no device arena")
-            if engine is not None and getattr(engine, "dense_optimizer", False):
-                self.sharded = False               # torch's dense optimisers (-optim sgd|adagrad|adadelta) read the whole reduced gradient
+            if engine is not None and (getattr(engine, "dense_optimizer", False) or getattr(engine, "optim_method", "adam") != "adam"):
+                # -optim sgd|adagrad|adadelta: all-reduce + the replicated HIP update (the sharded form is Adam's); torch's dense optimisers
+                # (Optim.torch_dense) read the whole reduced gradient as well
+                self.sharded = False
             if engine is not None and engine.dp is None:
                 # an error here must stop the run: `world` / `rank` set without `engine.dp` would train unsynchronised replicas
                 # plans built for one process carry the lazy row-wise update of the embedding tables (engine._build_row_tables): every

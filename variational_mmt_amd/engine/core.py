@@ -327,6 +327,7 @@ class Engine(StepAPI):
         `Engine.row_adam = False` restores the dense kernels."""
         names = ("encoder.embeddings.make_embedding.emb_luts.0.weight", "decoder.embeddings.make_embedding.emb_luts.0.weight")
         self._row_adam = False
+        self.optim_method = "adam"           # what optim_step launches (set_optim_method)
         self._lazy_dirty = False             # rows behind the step counter exist (an update has run since the last flush)
         self._in_step = 0                    # > 0: inside forward / loss_backward / optim_step / a flush (reads of the arena are the engine's own)
         self.lazy_roll = 16                  # every row is brought up to date at least every `lazy_roll` updates (<= LAZY_HIST / 4)
@@ -408,7 +409,21 @@ class Engine(StepAPI):
         return self.dp is not None and self.dp.active()
 
     def rows_active(self):
-        return bool(self.row_tables) and self.row_adam and not self.dp_on()
+        # (Adadelta's state decays on a zero gradient and there is no lazy form of it here: its tables take the dense kernel)
+        return bool(self.row_tables) and self.row_adam and not self.dp_on() and self.optim_method != "adadelta"
+
+    def set_optim_method(self, method):
+        """the update optim_step launches: "adam" (csrc/optim.hip) or "sgd" / "adagrad" / "adadelta" (csrc/optim_methods.hip), state in
+        flat_m / flat_v (vmmt.h).  Called between steps (Optim.set_parameters): every row of the tables is brought up to date under the
+        method that left it behind, and the plans are rebuilt -- whether they carry the row entries depends on the method."""
+        if method != "adam" and method not in L.OPTIM_METHODS:
+            raise RuntimeError("Invalid optim method: %s" % method)
+        if method == self.optim_method:
+            return
+        on = self._row_adam
+        self.row_adam = False              # (flush, held-back half out, plans dropped, the tables' gradients cleared)
+        self.optim_method = method
+        self.row_adam = on
 
     def flush_lazy_rows(self, stream=None):
         """every row of the embedding tables up to date for the step counter (vmmt_rows_catchup, mode 1), on the current stream behind
@@ -870,8 +885,8 @@ class Engine(StepAPI):
         codes = [w for w in (int(s[2].item()) for s in self.seq_syncs) if w]
         g = self._guard.tolist()
         skipped = g[1] // max(1, self._adam_launches)
-        # (-optim sgd|adagrad|adadelta: torch's dense optimisers do not read the guard -- the steps since the timeout may have applied
-        #  garbage gradients: nothing to continue from)
+        # (Optim.torch_dense, the torch twin of -optim sgd|adagrad|adadelta: torch's dense optimisers do not read the guard -- the steps
+        #  since the timeout may have applied garbage gradients: nothing to continue from)
         if not self.seq_fallback or getattr(self, "dense_optimizer", False):
             raise RuntimeError("persistent LSTM launch(es) reported a hand-off timeout (error words %s, guard 0x%x): results invalid; "
                                "rerun with VMMT_PERSISTENT_LSTM=0" % ([hex(c) for c in codes], g[0]))

@@ -152,18 +152,25 @@ class StepAPI(object):
                     elbo=nmt - img_logprob + kl_after, n_words=int(round(s[L.STAT_NWORDS])),
                     n_correct=int(round(s[L.STAT_NCORRECT])))
 
-    def optim_step(self, lr=0.002, max_grad_norm=5.0, beta1=0.9, beta2=0.999, eps=1e-9, grad_scale=1.0):
+    def optim_step(self, lr=0.002, max_grad_norm=5.0, beta1=0.9, beta2=0.999, eps=1e-9, grad_scale=1.0, method="adam"):
         """Optim.step (Optim.py:78-96): global-norm clip + Adam over the arena, then the compute shadows are refreshed.
+        `method`: "adam", or "sgd" / "adagrad" / "adadelta" (csrc/optim_methods.hip: only `lr` is used, the betas and eps are Adam's) --
+        the same schedule, only the launched entry differs; it is the method the engine was told (set_optim_method: the plans of the
+        training forward depend on whether the embedding tables are updated by row).
         The arena is updated in two halves: [encoder | inference networks] on the current stream (the next forward needs
         them first), [generator | attention | decoder] on the side stream, where it overlaps the next step's encoder
         phase; the forward plan waits on `opt_side_done` before it touches decoder-side weights."""
         self._in_step += 1
         try:
-            return self._optim_step(lr, max_grad_norm, beta1, beta2, eps, grad_scale)
+            return self._optim_step(lr, max_grad_norm, beta1, beta2, eps, grad_scale, method)
         finally:
             self._in_step -= 1
 
-    def _optim_step(self, lr, max_grad_norm, beta1, beta2, eps, grad_scale):
+    def _optim_step(self, lr, max_grad_norm, beta1, beta2, eps, grad_scale, method="adam"):
+        if method != self.optim_method:
+            raise RuntimeError("optim_step(method=%r): the engine is set up for %r; call set_optim_method() before the training forward"
+                               % (method, self.optim_method))
+        code = None if method == "adam" else L.OPTIM_METHODS[method]        # (Adam has entry points of its own)
         main = torch.cuda.current_stream(self.dev)
         st = main.cuda_stream
         self._flush_bg()                # (two updates without a forward between them)
@@ -171,6 +178,8 @@ class StepAPI(object):
         guard = self._guard.data_ptr()
         n_launch = [0]
         if self.dp_on() and self.dp.sharded:
+            if code is not None:
+                raise RuntimeError("-optim %s: the sharded data-parallel update is Adam's; set dp.sharded = False before the first step" % method)
             return self._optim_step_sharded(lr, max_grad_norm, beta1, beta2, eps, grad_scale)
         if self.dp_on():                # replicated data-parallel update: every rank must skip the same steps
             self.finish_allreduce()
@@ -205,7 +214,13 @@ class StepAPI(object):
 
         def adam_range(lo, hi, stream, shadow=None):
             blocks = int(self.bg_adam_blocks) if stream != st else int(self.fg_adam_blocks)
-            if hi > lo:
+            if hi > lo and code is not None:
+                L.check(self.lib.vmmt_optim_step_ranges(code, self.flat_p.data_ptr() + 4 * lo, self.flat_g.data_ptr() + 4 * lo,
+                                                        self.flat_m.data_ptr() + 4 * lo, self.flat_v.data_ptr() + 4 * lo, hi - lo, 0, 0, lr,
+                                                        float(max_grad_norm or 0.0), self._sumsq.data_ptr(), grad_scale, blocks, shadow, 0,
+                                                        hi - lo if shadow else 0, guard, stream), "vmmt_optim_step_ranges")
+                n_launch[0] += 1
+            elif hi > lo:
                 L.check(self.lib.vmmt_adam_step(self.flat_p.data_ptr() + 4 * lo, self.flat_g.data_ptr() + 4 * lo,
                                                 self.flat_m.data_ptr() + 4 * lo, self.flat_v.data_ptr() + 4 * lo, hi - lo, lr, beta1, beta2,
                                                 eps, t_adam, float(max_grad_norm or 0.0), self._sumsq.data_ptr(), grad_scale,
@@ -214,7 +229,7 @@ class StepAPI(object):
 
         rows = self.rows_active()
         if rows:
-            if (beta1, beta2, eps) != self._adam_consts:
+            if code is None and (beta1, beta2, eps) != self._adam_consts:
                 # the replayed zero-gradient steps use the run's betas / eps: a change brings every row up to date under the old ones first
                 self.flush_lazy_rows()
                 self._adam_consts = (beta1, beta2, eps)
@@ -224,6 +239,14 @@ class StepAPI(object):
 
         def rows_step(t, stream):
             o = 4 * t["off"]
+            if code is not None:
+                # SGD / Adagrad: the flagged rows only; the ring and `last` are kept going for the catch-up entries (nothing to replay)
+                L.check(self.lib.vmmt_optim_rows_step(code, self.flat_p.data_ptr() + o, self.flat_g.data_ptr() + o, self.flat_m.data_ptr() + o,
+                                                      t["R"], t["C"], t["flags"].data_ptr(), t["last"].data_ptr(), t["hist"].data_ptr(), lr,
+                                                      t_adam, roll, float(max_grad_norm or 0.0), self._sumsq.data_ptr(), grad_scale, guard,
+                                                      stream), "vmmt_optim_rows_step")
+                n_launch[0] += 1
+                return
             L.check(self.lib.vmmt_adam_rows_step(self.flat_p.data_ptr() + o, self.flat_g.data_ptr() + o, self.flat_m.data_ptr() + o,
                                                  self.flat_v.data_ptr() + o, t["R"], t["C"], t["flags"].data_ptr(), t["last"].data_ptr(),
                                                  t["hist"].data_ptr(), lr, beta1, beta2, eps, t_adam, roll, float(max_grad_norm or 0.0),
@@ -247,7 +270,13 @@ class StepAPI(object):
                 blocks = int(self.bg_adam_blocks) if stream != st else int(self.fg_adam_blocks)
                 h_lo, h_n = (tb[0][0] - lo, tb[0][1] - tb[0][0]) if tb else (0, 0)
                 s_ptr, s_lo, s_n = (sh[0][2][1], sh[0][0] - lo, sh[0][1] - sh[0][0]) if sh else (None, 0, 0)
-                if hi - lo - h_n > 0:
+                if hi - lo - h_n > 0 and code is not None:
+                    L.check(self.lib.vmmt_optim_step_ranges(code, self.flat_p.data_ptr() + 4 * lo, self.flat_g.data_ptr() + 4 * lo,
+                                                            self.flat_m.data_ptr() + 4 * lo, self.flat_v.data_ptr() + 4 * lo, hi - lo, h_lo, h_n, lr,
+                                                            float(max_grad_norm or 0.0), self._sumsq.data_ptr(), grad_scale, blocks, s_ptr, s_lo,
+                                                            s_n, guard, stream), "vmmt_optim_step_ranges")
+                    n_launch[0] += 1
+                elif hi - lo - h_n > 0:
                     L.check(self.lib.vmmt_adam_step_ranges(self.flat_p.data_ptr() + 4 * lo, self.flat_g.data_ptr() + 4 * lo,
                                                            self.flat_m.data_ptr() + 4 * lo, self.flat_v.data_ptr() + 4 * lo, hi - lo, h_lo, h_n, lr,
                                                            beta1, beta2, eps, t_adam, float(max_grad_norm or 0.0), self._sumsq.data_ptr(), grad_scale,

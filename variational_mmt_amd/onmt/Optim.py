@@ -1,6 +1,11 @@
 """Mirror of onmt.Optim (reference: onmt/Optim.py:34-114): same constructor, `set_parameters`, `step`,
 `update_learning_rate`, `.lr`, `.optimizer`; for method 'adam' (every reference recipe) the update is ONE fused HIP
-kernel over the engine's flat arena (global-norm clip + Adam, eps = 1e-9).
+kernel over the engine's flat arena (global-norm clip + Adam, eps = 1e-9).  Methods 'sgd' (the reference's default), 'adagrad' and
+'adadelta' run on the same schedule with the kernels of csrc/optim_methods.hip: the optimiser state lives in the arena where Adam's
+moments live (Adagrad `sum` in flat_m; Adadelta `square_avg` in flat_m, `acc_delta` in flat_v), `.optimizer` is an arena-backed
+stand-in (_ArenaOptim) whose state_dict has torch's own layout.  `Optim.torch_dense = True` hands these three methods to torch.optim on
+views of the arena instead (no row-wise tables, no device-side guard, a shadow refresh that reads every parameter back): the comparison
+twin of the HIP update.
 
 Checkpoint format (TrainerMultimodal.py:580-587 pickles the whole object as checkpoint['optim']): this class pickles to
 what the reference's does -- `params` = list of nn.Parameter, `optimizer` = a genuine torch.optim.Adam over them with its
@@ -50,8 +55,48 @@ class _ArenaAdam(object):
             self._optim._push_state(sd)
 
 
+_TORCH_CLS = {"sgd": torch.optim.SGD, "adagrad": torch.optim.Adagrad, "adadelta": torch.optim.Adadelta}
+# torch's per-parameter state tensors of each method, in the order (flat_m, flat_v) holds them (include/vmmt.h)
+_STATE_KEYS = {"adam": ("exp_avg", "exp_avg_sq"), "sgd": (), "adagrad": ("sum",), "adadelta": ("square_avg", "acc_delta")}
+
+
+class _ArenaOptim(_ArenaAdam):
+    """stands where torch.optim.SGD / Adagrad / Adadelta stand in the reference's Optim (Optim.py:58-67)"""
+
+    def __init__(self, method, lr):
+        self.method = method
+        group = dict(_TORCH_CLS[method]([nn.Parameter(torch.zeros(1))], lr=lr).param_groups[0])     # torch's own defaults and keys
+        group.pop("params")
+        self.param_groups = [group]
+        self._saved = None
+        self._optim = None
+
+    def param_state(self, p):
+        """torch's state entry of one parameter out of the arena, on the CPU (None: torch would hold none)"""
+        e = self._optim.engine
+        name = getattr(p, "_vmmt_name", None)
+        keys = _STATE_KEYS[self.method]
+        # (Adagrad creates its state with the optimiser, Adadelta at a parameter's first gradient; SGD without momentum has none)
+        if not keys or name is None or name not in e.grads or (self.method == "adadelta" and e.step_count == 0):
+            return None
+        off, shp = e.offsets[name]
+        n = p.numel()
+        st = {"step": torch.tensor(float(e.step_count), device="cpu")}
+        for key, flat in zip(keys, (e.flat_m, e.flat_v)):
+            st[key] = flat[off:off + n].view(*shp).detach().cpu().clone()
+        return st
+
+    def state_dict(self):
+        o = self._optim
+        if o is None or o.engine is None:
+            return self._saved or {"state": {}, "param_groups": self.param_groups}
+        state = {i: st for i, st in ((i, self.param_state(p)) for i, p in enumerate(o.params)) if st is not None}
+        return {"state": state, "param_groups": [dict(self.param_groups[0], params=list(range(len(o.params))))]}
+
+
 class Optim(object):
     resume_adam_state = False      # see the module docstring: False = as executed by the reference
+    torch_dense = False            # True: -optim sgd|adagrad|adadelta through torch.optim on the arena views (the comparison twin)
 
     def __init__(self, method, lr, max_grad_norm, lr_decay=1, start_decay_at=None, beta1=0.9, beta2=0.999,
                  adagrad_accum=0.0, decay_method=None, warmup_steps=4000, model_size=None):
@@ -81,6 +126,10 @@ class Optim(object):
         if len(engines) != 1:
             raise RuntimeError("Optim.set_parameters expects the parameters of one variational_mmt_amd model")
         self.engine = list(engines.values())[0]
+        if self.method not in _STATE_KEYS:
+            raise RuntimeError("Invalid optim method: " + self.method)
+        if not (self.torch_dense and self.method != "adam"):
+            self.engine.set_optim_method(self.method)
         if self.method == "adam":
             saved = None
             if self.resume_adam_state and self.optimizer is not None:
@@ -96,8 +145,19 @@ class Optim(object):
             e.step_count = 0
             if saved is not None:
                 self._push_state(saved)
-        elif self.method in ("sgd", "adagrad", "adadelta"):
-            # not on the hot path (every reference recipe uses adam): thin delegation to torch on the arena views
+        elif not self.torch_dense:
+            # a NEW optimiser, as in the reference (Optim.py:58-67): state zeroed, Adagrad's `sum` filled with adagrad_accum, step 0
+            self.optimizer = _ArenaOptim(self.method, self.lr)
+            self.optimizer.bind(self)
+            e = self.engine
+            if e.dp is not None:
+                e.dp.sharded = False      # all-reduce + the replicated HIP update (the sharded reduce-scatter form is Adam's)
+            e.wait_background()
+            e.flat_m.fill_(float(self.adagrad_accum) if self.method == "adagrad" else 0.0)
+            e.flat_v.zero_()
+            e.step_count = 0
+        else:
+            # the comparison twin: thin delegation to torch on the arena views
             self.engine.row_adam = False           # torch's dense optimisers on the arena views read / clear the whole gradient
             # ... and the whole REDUCED gradient under data parallelism: all-reduce + replicated update instead of the sharded
             # optimiser's reduce-scatter (which leaves the sum in this rank's 1 / world of every segment only)
@@ -105,10 +165,7 @@ class Optim(object):
             if self.engine.dp is not None:
                 self.engine.dp.sharded = False
             self.engine.drop_workspaces()
-            cls = {"sgd": torch.optim.SGD, "adagrad": torch.optim.Adagrad, "adadelta": torch.optim.Adadelta}[self.method]
-            self.optimizer = cls(self.params, lr=self.lr)
-        else:
-            raise RuntimeError("Invalid optim method: " + self.method)
+            self.optimizer = _TORCH_CLS[self.method](self.params, lr=self.lr)
 
     def _remap_state(self, state, old_params):
         """optimizer state of a checkpoint is keyed by the parameter's position in the WRITER's model.parameters() -- the
@@ -130,7 +187,7 @@ class Optim(object):
         return out
 
     def _push_state(self, sd):
-        """torch.optim.Adam state-dict layout: state keyed by the parameter's position in param_groups[0]['params'], which is
+        """torch's optimiser state-dict layout: state keyed by the parameter's position in param_groups[0]['params'], which is
         the position in `self.params` (both follow model.parameters())"""
         e = self.engine
         step = 0
@@ -138,8 +195,8 @@ class Optim(object):
             p = self.params[int(i)]
             off, shp = e.offsets[p._vmmt_name]
             n = p.numel()
-            e.flat_m[off:off + n].copy_(st["exp_avg"].reshape(-1))
-            e.flat_v[off:off + n].copy_(st["exp_avg_sq"].reshape(-1))
+            for key, flat in zip(_STATE_KEYS[self.method], (e.flat_m, e.flat_v)):
+                flat[off:off + n].copy_(st[key].reshape(-1))
             step = max(step, int(float(st["step"])))
         e.step_count = step
 
@@ -152,13 +209,13 @@ class Optim(object):
         if self.decay_method == "noam":
             self._set_rate(self.original_lr * (self.model_size ** (-0.5) *
                                                min(self._step ** (-0.5), self._step * self.warmup_steps ** (-1.5))))
-        if self.method == "adam":
+        if isinstance(self.optimizer, _ArenaAdam):
             self.engine.optim_step(lr=self.lr, max_grad_norm=self.max_grad_norm or 0.0, beta1=self.betas[0], beta2=self.betas[1],
-                                   eps=1e-9)
+                                   eps=1e-9, method=self.method)
         else:
             # torch's dense optimisers know nothing of the engine's guard word (a persistent recurrence that timed out left garbage
-            # gradients; the arena Adam kernels read the guard on the device and skip): look before every update -- a synchronisation,
-            # off the hot path (every reference recipe uses adam) -- and on every data-parallel rank together
+            # gradients; the arena kernels read the guard on the device and skip): look before every update -- a synchronisation,
+            # the twin is not a hot path -- and on every data-parallel rank together
             e = self.engine
             if e.dp_on():
                 e.finish_allreduce()
@@ -197,6 +254,15 @@ class Optim(object):
             if t is None:
                 t = p.detach().cpu().clone()
             cpu_params.append(nn.Parameter(t, requires_grad=True))
+        if isinstance(self.optimizer, _ArenaOptim):        # the genuine torch class with the arena's state, as the reference pickles it
+            opt = _TORCH_CLS[self.method](cpu_params, lr=self.lr)
+            for q, p in zip(cpu_params, self.params):
+                st = self.optimizer.param_state(p)
+                if st is not None:
+                    opt.state[q] = st
+            d["params"] = cpu_params
+            d["optimizer"] = opt
+            return d
         adam = torch.optim.Adam(cpu_params, lr=self.lr, betas=tuple(self.betas), eps=1e-9)
         if e.step_count > 0:
             for q, p in zip(cpu_params, self.params):

@@ -135,7 +135,8 @@ _TRAIN = [
         ("-valid_batch_size", int, 32, dict(help="validation minibatch")),
         ("-max_generator_batches", int, 32, dict(help="target rows per loss shard in the reference; the fused vocabulary sweep takes all rows at once")),
         ("-epochs", int, 13, dict(help="last epoch")),
-        ("-optim", None, "sgd", dict(choices=["sgd", "adagrad", "adadelta", "adam"], help="optimiser; adam (and sgd) on the MI355X path")),
+        ("-optim", None, "sgd", dict(choices=["sgd", "adagrad", "adadelta", "adam"], help="optimiser; all four are fused HIP updates over the parameter arena "
+                                                                                   "(adadelta updates the embedding tables densely)")),
         ("-adagrad_accumulator_init", float, 0, dict(help="adagrad accumulator start value")),
         ("-max_grad_norm", float, 5, dict(help="global gradient-norm clip")),
         ("-dropout", float, 0.3, dict(help="dropout between LSTM layers and on the decoder output")),
