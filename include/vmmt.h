@@ -644,6 +644,29 @@ int vmmt_optim_step_ranges(int method, float* p, const float* g, float* s1, floa
 int vmmt_optim_rows_step(int method, float* p, const float* g, float* s1, int R, int C, const int32_t* flags, int32_t* last, int32_t* hist, float lr,
                          int step, int roll, float max_norm, const float* sumsq, float grad_scale, const int32_t* skip, void* stream);
 
+/* ---- -label_smoothing (onmt/Loss.py:146-166, onmt/VILoss.py:231-243,479-482): exact corrections behind the plain generator passes -------
+ * eps = label_smoothing in (0, 1], u = eps / (V - 2), V >= 3; the target distribution of a token row is u on every non-pad column, 1 - eps at
+ * y_m, 0 at pad, and 0 everywhere for a row with y_m = pad.  With s_m = [y_m != pad] inv_norm, wbar = sum_{j != pad} W[j,:], bbar = sum_{j != pad}
+ * bias[j], obar = sum_m s_m o_m, sigma = sum_m s_m (csrc/label_smoothing.hip):
+ *   vmmt_ls_colsum  wbar (f32 [H]) and bbar (one float) from the compute copy W [V][ldw] (f32 / bf16) and the f32 bias
+ *   vmmt_ls_rows    sums[0] = sum_m loss_m, the smoothed KL-divergence sum (stored, not accumulated), from lse and tok_nll of the plain pass;
+ *                   with dO != NULL also dO_m += s_m ((eps + u) W[y_m] - u wbar) in place (f32 [M][lddo]), obar (f32 [H]) and sums[1] = sigma.
+ *                   dO = NULL: the loss alone (W, obar may be NULL, inv_norm is ignored)
+ *   vmmt_ls_dW      dW[v] -= u obar, db[v] -= u sigma for v != pad; dW[y_m] += (eps + u) s_m o_m, db[y_m] += (eps + u) s_m
+ * rows: the compacted-token list of the combine (token m of the launch is row rows[m] of O, y, lse, tok_nll and dO; < 0: no token), or NULL.
+ * O, W: rows 16-byte aligned, readable up to the next multiple of 8 (bf16) / 4 (f32) columns; lddo a multiple of 4; H <= 1024.
+ * scratch: vmmt_ls_ws_floats(M, V, H) floats (M: the largest token count), shared by _colsum and _rows (disjoint parts).
+ * No allocation, asynchronous on `stream`.  No float atomics except the per-token part of vmmt_ls_dW, where vmmt_gen_dW_finish's one-hot term
+ * uses them too (tokens share target rows): wbar, bbar, obar, sums and dO are bit-reproducible (fixed partitions folded in a fixed order). */
+int64_t vmmt_ls_ws_floats(int M, int V, int H);
+int vmmt_ls_colsum(int dtype, const void* W, int64_t ldw, const float* bias, int V, int H, int pad, float* wbar, float* bbar, float* scratch,
+                   void* stream);
+int vmmt_ls_rows(int dtype, const void* O, int64_t ldo, const void* W, int64_t ldw, const int64_t* y, const int32_t* rows, int M, int V, int H,
+                 int pad, float eps, float inv_norm, const float* lse, const float* tok_nll, const float* wbar, const float* bbar, float* dO,
+                 int64_t lddo, float* obar, float* sums, float* scratch, void* stream);
+int vmmt_ls_dW(int dtype, const void* O, int64_t ldo, const int64_t* y, const int32_t* rows, int M, int V, int H, int pad, float eps,
+               float inv_norm, const float* obar, const float* sums, float* dW, int64_t lddw, float* db, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

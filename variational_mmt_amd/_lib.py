@@ -166,6 +166,10 @@ _SIGS = {
     "vmmt_sumsq_rows": (i32, [vp, i32, i32, vp, vp, vp, vp, i32, vp]),
     "vmmt_optim_step_ranges": (i32, [i32, vp, vp, vp, vp, i64, i64, i64, f32, f32, vp, f32, i32, vp, i64, i64, vp, vp]),
     "vmmt_optim_rows_step": (i32, [i32, vp, vp, vp, i32, i32, vp, vp, vp, f32, i32, i32, f32, vp, f32, vp, vp]),
+    "vmmt_ls_ws_floats": (i64, [i32, i32, i32]),
+    "vmmt_ls_colsum": (i32, [i32, vp, i64, vp, i32, i32, i32, vp, vp, vp, vp]),
+    "vmmt_ls_rows": (i32, [i32, vp, i64, vp, i64, vp, vp, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp]),
+    "vmmt_ls_dW": (i32, [i32, vp, i64, vp, vp, i32, i32, i32, i32, f32, f32, vp, vp, vp, i64, vp, vp]),
 }
 
 EXPORTS = sorted(_SIGS)

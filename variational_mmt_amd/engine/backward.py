@@ -39,6 +39,44 @@ class BackwardPlan(object):
         #  Cache, was measured with tools/ab.py: 2.227-2.97 ms against 2.213 ms in one pass -- not kept)
         self._patch = {}
         self._src_rows_normed = False
+        # -label_smoothing (csrc/label_smoothing.hip; eps = 0: none of these entries): exact corrections behind the plain generator passes
+        ls = self.ls_eps > 0
+        self._ls_rows_entry = self._ls_dw_entry = None
+        Og = self.O if (training_dropout and d.dropout > 0) else self.AH       # the generator's input as the dWg passes read it
+        ls_head_done = [False]
+
+        def ls_rows():
+            # main: dO_m += s_m ((eps + u) Wg[y_m] - u wbar), the smoothed loss sum, obar / sigma -- behind the launch that completes the plain
+            # dO, in front of the output layer's backward; wbar came out of the loss plan's side stream (`ls_wbar`)
+            q = self.ls_ptr
+            e._wait(P, "ls_wbar")
+            self._patch["ls_rows"] = (len(P), 12)
+            self._ls_rows_entry = len(P)
+            e._call(P, lib.vmmt_ls_rows, dt, Og.p(), Og.ld, wg.p(), wg.ld, self.y.data_ptr(), None, M, V, H, PAD, self.ls_eps, inv_norm,
+                    self.lse.data_ptr(), self.tok_nll.data_ptr(), q["wbar"], q["bbar"], self.dO32.p(), self.dO32.ld, q["obar"], q["sums"],
+                    q["scratch"])
+            e._record(P, "ls_obar")
+
+        def ls_dw():
+            # the stream of dWg / db: dWg -= u 1 (x) obar, += (eps + u) s_m o_m at row y_m, the two db terms -- behind the launch that completes
+            # the plain dWg and db, in front of the generator segment's reduction and its piece of the gradient norm
+            q = self.ls_ptr
+            e._wait(P, "ls_obar")
+            self._patch["ls_dw"] = (len(P), 10)
+            self._ls_dw_entry = len(P)
+            e._call(P, lib.vmmt_ls_dW, dt, Og.p(), Og.ld, self.y.data_ptr(), None, M, V, H, PAD, self.ls_eps, inv_norm, q["obar"], q["sums"],
+                    e.gp("generator.0.weight"), H, e.gp("generator.0.bias"))
+
+        def gen_dO_tail():
+            # main: [the second half of the sweep's fold,] [the smoothing correction of dO]
+            e._sid = MAIN
+            ls_head_done[0] = True
+            if self.gen_fused and getattr(self, "_combine_split", False):
+                self._comb_dO_entry = len(P)
+                self._patch["comb_dO"] = (len(P), 10)
+                e._call(P, lib.vmmt_gen_fwd_combine_dO, *self._combine_args)
+            if ls and self.gen_fused:
+                ls_rows()
         if self.gen_fused:
             pass        # dO32 came out of the loss plan (vmmt_gen_fwd_dO); dWg / db: one GEMM + vmmt_gen_dW_finish on the side stream below
         elif fuse_db:
@@ -53,6 +91,8 @@ class BackwardPlan(object):
             e._record(P, "GT")
             e._gemm(P, L.GEMM_TN, self.GT.p(), self.GT.ld, wg.p(), wg.ld, self.dO32.p(), self.dO32.ld, M, H, V, out_f32=1,
                     split_k=max(1, min(8, (1024 * 128 * 128) // max(1, M * H))))
+            if ls:
+                ls_rows()
         # ================= aux: image term + its network (z is detached: independent of the text path) ==========
         rp = bool(e.reparam_grad)
         TGT = 3
@@ -206,10 +246,8 @@ class BackwardPlan(object):
         def main_head():
             # main: [dO: the second half of the sweep's fold,] dropout + tanh backward, linear_out, attention
             e._sid = MAIN
-            if self.gen_fused and getattr(self, "_combine_split", False):
-                self._comb_dO_entry = len(P)
-                self._patch["comb_dO"] = (len(P), 10)
-                e._call(P, lib.vmmt_gen_fwd_combine_dO, *self._combine_args)
+            if not ls_head_done[0]:
+                gen_dO_tail()
             mlp = d.attn == "mlp"            # (no tanh behind linear_out: the activation backward is the dropout mask alone)
             e._call(P, lib.vmmt_act_bwd, dt, L.ACT_NONE if mlp else L.ACT_TANH, self.dO32.p(), self.dO32.ld, 1, self.AH.p(), self.AH.ld,
                     self.out_mask.p() if drop else None, self.out_mask.ld if drop else 0, self.dPre.p(), self.dPre.ld, M, H)
@@ -272,6 +310,10 @@ class BackwardPlan(object):
             if aux_before_side:
                 aux_chain()
         else:
+            if ls and self.gen_fused:
+                # label smoothing where the main stream's head is issued LAST (conditional model): the fold of dO and its correction go out
+                # first, so that `ls_obar` is recorded before the side stream's dWg pass, issued below, waits for it
+                gen_dO_tail()
             aux_chain()
         # side: dWg = G^T O as soon as G^T exists, underneath dO = G Wg of the main stream (measured, tools/ab.py: issuing it behind dR,
         # underneath the LSTM backward chains instead, is 3 % slower -- 2.333 vs 2.264 ms)
@@ -305,6 +347,8 @@ class BackwardPlan(object):
             e._gemm(P, L.GEMM_NN, self.GT.p(), self.GT.ld, self.O.p(), self.O.ld, e.gp("generator.0.weight"), H, V, H, M, out_f32=1)   # plain store
             if not fuse_db:
                 e._call(P, lib.vmmt_rowsum, dt, self.GT.p(), self.GT.ld, V, M, e.gp("generator.0.bias"))
+        if ls:
+            ls_dw()
         e._allreduce(P, "generator.0.weight", "decoder.attn.linear_out.weight")
         # the generator's share of the gradient norm (a quarter of the arena) right behind its product, on this stream, instead of in the
         # norm of the whole first half at the end of the decoder's parameter gradients (slot 7: free outside the conditional model)

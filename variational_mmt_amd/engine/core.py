@@ -73,6 +73,9 @@ class Engine(StepAPI):
         # through the KL.  True = the reparameterised estimator the paper describes (d z flows from the decoder input and the
         # image network into q(z|x)); tested against the oracle's reparam_grad=True (tests/test_gpu_step_parity.py)
         self.reparam_grad = False
+        # -label_smoothing (onmt/Loss.py:146-166): set by the loss object or by loss_backward(label_smoothing=) / loss(label_smoothing=); 0.0: the
+        # plain NLL and today's launch plans; a workspace's plans follow it (Workspace.set_label_smoothing)
+        self.label_smoothing = 0.0
         self.stats_host = None
         self._sid = 0
         # the side stream carries bulk work that is off the critical path: lowest hardware priority, so that small

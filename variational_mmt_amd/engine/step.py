@@ -104,18 +104,26 @@ class StepAPI(object):
         ws.training = training
         return ws
 
-    def loss(self, ws):
-        """statistics of _compute_loss without backward (monolithic_compute_loss, Loss.py:68-86)."""
+    def loss(self, ws, label_smoothing=None):
+        """statistics of _compute_loss without backward (monolithic_compute_loss, Loss.py:68-86).  label_smoothing: sets
+        Engine.label_smoothing (None: as it stands); > 0: the smoothed sum as well (read_stats)."""
         st = self.stream()
+        if label_smoothing is not None:
+            self.label_smoothing = float(label_smoothing)
+        ws.set_label_smoothing(self.label_smoothing)
         self._run(ws.plan_loss_train if ws.training else ws.plan_loss_eval, ws.events)
+        if ws.ls_eps > 0:               # the loss-only row pass (csrc/label_smoothing.hip), behind the column sums of the plan's side stream
+            self._run(ws.plan_ls_loss[bool(ws.training)], ws.events)
         L.check(self.lib.vmmt_image_loss(self.dt, ws.mu_v.p(), ws.mu_v.ld, ws.img.p(), ws.img.ld, ws.B, self.d.img, 0.0, None, 0,
                                          ws.stats.data_ptr(), st), "vmmt_image_loss")
         return ws
 
     def loss_backward(self, ws, normalization=None, batch_global=None, kl_mult=1.0, use_freebits=False, margin=0.0,
-                      zero_grad=True):
+                      zero_grad=True, label_smoothing=None):
         """sharded_compute_loss (Loss.py:88-132): loss statistics + `loss.div(normalization).backward()`
-        through the whole model into the gradient arena.  H3: all T' rows are used (monolithic semantics)."""
+        through the whole model into the gradient arena.  H3: all T' rows are used (monolithic semantics).
+        label_smoothing: sets Engine.label_smoothing (None: as it stands); > 0: the generator loss is the KL divergence against the smoothed
+        target distribution (Loss.py:146-166), as corrections behind the plain passes (csrc/label_smoothing.hip)."""
         st = self.stream()
         B = ws.B
         norm = float(normalization if normalization is not None else B)
@@ -123,6 +131,9 @@ class StepAPI(object):
         # the gradient arena was zeroed by the training forward plan (side stream); zero_grad=False is meaningless here
         if not ws.training:
             raise RuntimeError("loss_backward() after an eval-mode forward")
+        if label_smoothing is not None:
+            self.label_smoothing = float(label_smoothing)
+        ws.set_label_smoothing(self.label_smoothing)
         self._in_step += 1
         try:
             if ws._loss_patch is not None:          # fused generator: the statistics pass writes dO = dL/dO scaled by 1 / normalization
@@ -147,9 +158,14 @@ class StepAPI(object):
             kl_after = max(kl_after, margin)
         img_logprob = s[L.STAT_IMG_LOGPROB]
         nmt = s[L.STAT_NLL]
+        elbo = nmt - img_logprob + kl_after
+        if ws.ls_eps > 0:
+            # as executed by the reference: `nmt` is the smoothed KL-divergence sum, `elbo` minus the summed target log-likelihood alone
+            # (VILoss.py:243-244,479-480)
+            nmt, elbo = float(ws.ls_buf[0]), s[L.STAT_NLL]
         return dict(nmt=nmt, td_kl_before=kl_before, td_kl_after=kl_after, td_kl_multiplier=kl_mult,
                     img_feats_loss=img_logprob, img_feats_cos=s[L.STAT_IMG_COS] / float(ws.B),
-                    elbo=nmt - img_logprob + kl_after, n_words=int(round(s[L.STAT_NWORDS])),
+                    elbo=elbo, n_words=int(round(s[L.STAT_NWORDS])),
                     n_correct=int(round(s[L.STAT_NCORRECT])))
 
     def optim_step(self, lr=0.002, max_grad_norm=5.0, beta1=0.9, beta2=0.999, eps=1e-9, grad_scale=1.0, method="adam"):

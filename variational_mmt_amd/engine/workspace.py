@@ -164,6 +164,11 @@ class Workspace(BackwardPlan, ConditionalPlans):
             self._cond_alloc()
         self._keep = []
         self.events = {}
+        # -label_smoothing (csrc/label_smoothing.hip): 0.0 = today's plans, no buffer of its own
+        self.ls_eps, self.ls_buf, self.plan_ls_loss = 0.0, None, {}
+        if eng.label_smoothing > 0:
+            self.ls_eps = self._ls_check(eng.label_smoothing)
+            self._ls_alloc()
         self.plan_fwd_train = self._plan_forward(True)
         self.plan_fwd_eval = self._plan_forward(False)
         self.plan_loss_train = self._plan_loss(True)
@@ -569,6 +574,20 @@ class Workspace(BackwardPlan, ConditionalPlans):
         e._sid = 0
         # (the generator's third of the last optimiser step -- `opt_gen_done`, side or aux stream -- is behind the forward plan's last wait: see there)
         O = self.O if (training and d.dropout > 0) else self.AH      # eval: nn.Dropout is the identity
+        if self.ls_eps > 0:
+            # label smoothing: the generator weight's column sums need the refreshed shadow only -- on the side stream (idle here), beside the
+            # sweep; what reads them waits for `ls_wbar` (the backward plan's row pass, or the loss-only row pass behind this plan: Engine.loss)
+            q = self.ls_ptr
+            e._record(P, "ls_begin")
+            e._sid = 1
+            e._wait(P, "ls_begin")
+            e._call(P, lib.vmmt_ls_colsum, e.dt, wg.p(), wg.ld, e.pp("generator.0.bias"), d.vt, d.hid, PAD, q["wbar"], q["bbar"], q["scratch"])
+            e._record(P, "ls_wbar")
+            e._sid = 0
+            Pl = self.plan_ls_loss[bool(training)] = []
+            e._wait(Pl, "ls_wbar")
+            e._call(Pl, lib.vmmt_ls_rows, e.dt, O.p(), O.ld, None, 0, self.y.data_ptr(), None, self.M, d.vt, d.hid, PAD, self.ls_eps, 0.0,
+                    self.lse.data_ptr(), self.tok_nll.data_ptr(), q["wbar"], q["bbar"], None, 0, None, q["sums"], q["scratch"])
         if training:
             self._loss_patch = None
         if training and self.gen_fused:
@@ -596,6 +615,40 @@ class Workspace(BackwardPlan, ConditionalPlans):
                 self.tgt_logit.data_ptr(), self.lse.data_ptr(), self.tok_nll.data_ptr(), self.stats.data_ptr())
         return P
 
+    # ---------------------------------------------------------------------------------------------- label smoothing
+    def _ls_check(self, eps):
+        eps = float(eps)
+        if not 0.0 <= eps <= 1.0:
+            raise ValueError("label_smoothing must lie in [0, 1] (got %r)" % eps)
+        if eps > 0 and self.e.d.vt < 3:
+            raise ValueError("label_smoothing > 0 needs a target vocabulary of at least 3 entries (eps / (V - 2), onmt/Loss.py:159)")
+        return eps
+
+    def _ls_alloc(self):
+        """[smoothed loss sum, sigma, bbar, -] | wbar | obar | scratch of the kernels: one f32 buffer of this workspace"""
+        d = self.e.d
+        ldh = _ru(d.hid, 4)
+        n = int(self.e.lib.vmmt_ls_ws_floats(self.M, d.vt, d.hid))
+        self.ls_buf = torch.zeros(4 + 2 * ldh + n, dtype=torch.float32, device=self.e.dev)
+        b = self.ls_buf.data_ptr()
+        self.ls_ptr = dict(sums=b, bbar=b + 8, wbar=b + 16, obar=b + 16 + 4 * ldh, scratch=b + 16 + 8 * ldh)
+
+    def set_label_smoothing(self, eps):
+        """the plans of this workspace follow Engine.label_smoothing: rebuilt when it changes (between 0 and non-0 their entries differ)"""
+        eps = self._ls_check(eps)
+        if eps == self.ls_eps:
+            return
+        self.ls_eps = eps
+        if eps > 0 and self.ls_buf is None:
+            self._ls_alloc()
+        self.plan_ls_loss = {}
+        self.plan_loss_train = self._plan_loss(True)
+        self.plan_loss_eval = self._plan_loss(False)
+        self.plan_bwd, self._bwd_key = None, None
+        self.e._plan_tgt.clear()
+        if self.gen_fused and hasattr(self, "_tok_arg"):        # (the rebuilt loss plan takes this step's token count again)
+            self.set_token_count(self._tok_arg)
+
     # ---------------------------------------------------------------------------------------------- backward plan
     def kl_sum_ptr(self):
         """the KL sum the backward weighs against the free-bits margin: this rank's statistic, or under data parallelism its
@@ -621,6 +674,7 @@ class Workspace(BackwardPlan, ConditionalPlans):
         T' B: all rows, as the reference does).  Patches the launch plans: token count, row map, the vocabulary-slice geometry that
         follows the count"""
         e, M = self.e, self.M
+        self._tok_arg = n
         Mc = M if n is None else min(M, _ru(max(int(n), 1), 128))
         if not (self.gen_fused and e.gen_compact) or Mc not in self.gen_geo:
             Mc = M
@@ -654,6 +708,10 @@ class Workspace(BackwardPlan, ConditionalPlans):
         if getattr(self, "_comb_dO_entry", None) is not None:          # (the second half of the fold: as the loss plan's entry, set_token_count)
             fn, args, name, keep, sid = P[self._comb_dO_entry]
             P[self._comb_dO_entry] = (fn, args[:6] + (self.gen_Mc,) + args[7:22] + (os_stride, rows), name, keep, sid)
+        for ii, pos in ((self._ls_rows_entry, 6), (self._ls_dw_entry, 4)):     # label smoothing: (rows, M) of its row pass and its dWg pass
+            if ii is not None:
+                fn, args, name, keep, sid = P[ii]
+                P[ii] = (fn, args[:pos] + (rows, self.gen_Mc) + args[pos + 2:], name, keep, sid)
         self._bwd_tokens = self.gen_Mc
 
     def backward_plan(self, inv_norm, batch_global, kl_mult, use_freebits, margin, drop):

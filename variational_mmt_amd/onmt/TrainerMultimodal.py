@@ -52,10 +52,15 @@ class VIStatistics(object):
         if not self._pending:
             return
         from .. import _lib as L
-        vals = torch.stack([p[0] for p in self._pending]).tolist()          # one D2H copy
+        vecs = [p[0] for p in self._pending]
+        n = max(v.numel() for v in vecs)     # (label smoothing adds a slot: plain vectors among smoothed ones are padded)
+        vals = torch.stack([v if v.numel() == n else torch.nn.functional.pad(v, (0, n - v.numel())) for v in vecs]).tolist()   # one D2H copy
         for s, pend in zip(vals, self._pending):
             _t, B, Bg, mult, fb, margin = pend[:6]
             has_global = len(pend) > 6 and pend[6]
+            # label smoothing, as executed by the reference: `nmt` is the smoothed KL-divergence sum (slot STAT_COUNT), `elbo` minus the summed
+            # target log-likelihood alone -- no KL, no image term (VILoss.py:243-244,479-480)
+            smoothed = len(pend) > 7 and pend[7]
             # single process: Bg == B.  Data parallel: this rank's SHARE of the global figures (shares add up over the ranks to
             # the statistics of the single-process run on the whole minibatch); slot STAT_COUNT-1 carries the all-reduced KL sum
             kl_before = s[L.STAT_KL_SUM] / Bg
@@ -65,12 +70,12 @@ class VIStatistics(object):
                 if kl_glob < margin:
                     kl_after = margin * B / Bg
             v = self._v
-            v["nmt_loss"] += s[L.STAT_NLL]
+            v["nmt_loss"] += s[L.STAT_COUNT] if smoothed else s[L.STAT_NLL]
             v["td_kl_before"] += kl_before
             v["td_kl_after"] += kl_after
             v["image_feats_loss"] += s[L.STAT_IMG_LOGPROB]
             v["image_feats_cos"] += s[L.STAT_IMG_COS] / B
-            v["elbo_loss"] += s[L.STAT_NLL] - s[L.STAT_IMG_LOGPROB] + kl_after
+            v["elbo_loss"] += s[L.STAT_NLL] if smoothed else s[L.STAT_NLL] - s[L.STAT_IMG_LOGPROB] + kl_after
             v["n_words"] += int(round(s[L.STAT_NWORDS]))
             v["n_correct"] += int(round(s[L.STAT_NCORRECT]))
         self._pending = []

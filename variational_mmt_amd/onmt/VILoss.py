@@ -4,6 +4,8 @@ sharded_compute_loss == statistics + `loss.div(normalization).backward()` throug
 backward plan (the generator sharding of the reference is an autograd memory trick; all T' rows are used: hazard H3).
 KL annealing / free-bits state lives here as host scalars and advances once per call exactly like the reference
 (VILoss.py:463-473, 501-511; H8)."""
+import torch
+
 from .Loss import LossComputeBase
 from .TrainerMultimodal import VIStatistics
 
@@ -14,7 +16,12 @@ class NMTVIModel1LossCompute(LossComputeBase):
                  kl_annealing_warmup_steps=1000, image_loss_type="logprob", use_local_image_features=False,
                  two_step_image_prediction=False):
         super(NMTVIModel1LossCompute, self).__init__(generator, tgt_vocab)
-        assert label_smoothing == 0.0, "label smoothing is off in every reference recipe (opts.py:336); not on the hot path"
+        # label smoothing (Loss.py:146-166, VILoss.py:231-243): the KL divergence against the smoothed targets, as exact corrections behind
+        # the plain generator passes (csrc/label_smoothing.hip); the engine is told with every loss call
+        assert 0.0 <= label_smoothing <= 1.0, "label_smoothing must lie in [0, 1]"
+        if label_smoothing > 0 and len(tgt_vocab) < 3:
+            raise ValueError("label_smoothing > 0 needs a target vocabulary of at least 3 entries (label_smoothing / (len(tgt_vocab) - 2))")
+        self.label_smoothing = float(label_smoothing)
         assert image_loss_type == "logprob" and not use_local_image_features and not two_step_image_prediction, \
             "only the global-feature `logprob` image loss is on the hot path"
         assert self.padding_idx == 1, "kernels assume <blank> == 1 (onmt/io/DatasetBase.py)"
@@ -45,21 +52,24 @@ class NMTVIModel1LossCompute(LossComputeBase):
         has_global = dp is not None and dp.active() and ws.training
         if has_global:
             st[-1] = ws.kl_global[0]       # the all-reduced KL sum the backward compared with the free-bits margin (spare slot)
+        smoothed = ws.ls_eps > 0
+        if smoothed:                       # one more slot behind the statistics vector: the smoothed KL-divergence sum (VILoss.py:243-244)
+            st = torch.cat([st, ws.ls_buf[:1]])
         return VIStatistics(self.multimodal_model_type, pending=(st, ws.B, float(self.batch_global or ws.B), mult,
-                                                                 self.use_kl_freebits, self.kl_freebits_margin, has_global))
+                                                                 self.use_kl_freebits, self.kl_freebits_margin, has_global, smoothed))
 
     def sharded_compute_loss(self, batch, output, attns, cur_trunc, trunc_size, shard_size, normalization):
         ws = attns["_ws"]
         mult = self.kl_annealing_current if self.use_kl_annealing else 1.0
         ws.e.loss_backward(ws, normalization=float(normalization), batch_global=float(self.batch_global or ws.B), kl_mult=mult,
-                           use_freebits=self.use_kl_freebits, margin=self.kl_freebits_margin)
+                           use_freebits=self.use_kl_freebits, margin=self.kl_freebits_margin, label_smoothing=self.label_smoothing)
         st = self._stats(ws, mult)
         self._after_loss()
         return st
 
     def monolithic_compute_loss(self, batch, output, attns):
         ws = attns["_ws"]
-        ws.e.loss(ws)
+        ws.e.loss(ws, label_smoothing=self.label_smoothing)
         mult = self.kl_annealing_current if self.use_kl_annealing else 1.0
         st = self._stats(ws, mult)
         self._after_loss()

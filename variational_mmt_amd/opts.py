@@ -144,7 +144,8 @@ _TRAIN = [
         ("-truncated_decoder", int, 0, dict(help="truncated BPTT (0 on the MI355X path)")),
         ("-adam_beta1", float, 0.9, dict(help="Adam beta1")),
         ("-adam_beta2", float, 0.999, dict(help="Adam beta2")),
-        ("-label_smoothing", float, 0.0, dict(help="label smoothing (0 on the MI355X path)")),
+        ("-label_smoothing", float, 0.0, dict(help="label smoothing epsilon in [0, 1]: the generator loss becomes the KL divergence against targets smoothed over "
+                                                         "the non-pad vocabulary (epsilon / (V - 2) each); 0 = plain NLL")),
     ]),
     ("Optimization- Rate", [
         ("-learning_rate", float, 1.0, dict(help="initial learning rate")),
