@@ -445,4 +445,30 @@ inline int check_launch() {
   return e == hipSuccess ? VMMT_OK : VMMT_ELAUNCH;
 }
 
+// ----------------------------------------------------------------------------------------------
+// Shared by the time-step kernels of both cells (lstm.hip, gru.hip)
+// ----------------------------------------------------------------------------------------------
+typedef __attribute__((address_space(3))) void lds_void_t;
+typedef __attribute__((address_space(1))) const void glb_cvoid_t;
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
+
+// LDS-DMA: 16 bytes per lane from global memory straight into LDS (the destination is wave-uniform: lane l lands at dst + 16 l)
+__device__ __forceinline__ void dma16(const char* src, char* dst_uniform) {
+  __builtin_amdgcn_global_load_lds((glb_cvoid_t*)src, (lds_void_t*)dst_uniform, 16, 0, 0);
+}
+
+// host: may a bf16 operand be fetched in 16-byte pieces (base and every row 16-byte aligned)?
+inline bool al16(const void* p, long ld_elems) { return (((uintptr_t)p) & 15) == 0 && (ld_elems * 2) % 16 == 0; }
+
+// host: a whole recurrence in one call -- `nsteps` consecutive launches of `step`, step i described by dirs[i*ndir .. i*ndir+ndir)
+template <class Dir, class Step>
+inline int chain_steps(int ndir, int nsteps, const Dir* dirs, Step step) {
+  if (nsteps < 0 || !dirs) return VMMT_EINVAL;
+  for (int i = 0; i < nsteps; ++i) {
+    int rc = step(dirs + (long)i * ndir);
+    if (rc != VMMT_OK) return rc;
+  }
+  return VMMT_OK;
+}
+
 }  // namespace vmmt

@@ -229,14 +229,6 @@ __global__ void __launch_bounds__(256) gru_step_bwd_kernel(GruArgsB a) {
 // ==============================================================================================================
 // bf16 fast kernels (see the header comment for the split)
 // ==============================================================================================================
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void glb_cvoid_t;
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void gru_dma16(const char* src, char* dst_uniform) {
-  __builtin_amdgcn_global_load_lds((glb_cvoid_t*)src, (lds_void_t*)dst_uniform, 16, 0, 0);
-}
-
 constexpr int GRU_FOLD_F = 8 * 2 * 3 * 4 * 64 * 4;      // forward fold buffer: [slice][half][gate][reg][lane] f32 = 48 KiB
 constexpr int GRU_FOLD_B = 8 * 2 * 4 * 64 * 4;          // backward: [slice][half][reg][lane] f32 = 16 KiB
 
@@ -284,7 +276,7 @@ __global__ void __launch_bounds__(512) gru_step_fwd_fast(GruArgsF a) {
         const int r = wave + 8 * j;                                 // staged row: gate r >> 4, unit u0 + (r & 15)
         const long row = (long)(r >> 4) * H + u0 + (r & 15);
         const int sc = lane ^ Cf::key(r);                           // source chunk of this lane's LDS slot
-        if (sc * 8 < kleft) gru_dma16(wp + (row * d.ld_w + k0) * 2 + sc * 16, lds + r * ROWB);
+        if (sc * 8 < kleft) dma16(wp + (row * d.ld_w + k0) * 2 + sc * 16, lds + r * ROWB);
       }
     }
     u32x4 af[2][PER];
@@ -377,7 +369,7 @@ __global__ void __launch_bounds__(512) gru_step_bwd_fast(GruArgsB a) {
           const int p = wave + 8 * j;                               // piece: row p / 3, gate block p % 3
           const int r = p / 3, g = p % 3;
           const int sc = lane ^ Cf::key(r);
-          if (sc * 8 < kleft) gru_dma16(wp + ((long)(u0 + r) * d.ld_wt + (long)g * H + k0) * 2 + sc * 16, lds + r * ROWB + g * SEGB);
+          if (sc * 8 < kleft) dma16(wp + ((long)(u0 + r) * d.ld_wt + (long)g * H + k0) * 2 + sc * 16, lds + r * ROWB + g * SEGB);
         }
       }
       u32x4 af[2][PER];
@@ -438,8 +430,6 @@ static int gru_launch_bwd_fast(const GruArgsB& a, int ndir, hipStream_t st) {
   return check_launch();
 }
 
-static bool gru_al16(const void* p, long ld_elems) { return (((uintptr_t)p) & 15) == 0 && (ld_elems * 2) % 16 == 0; }
-
 static void fill_f(GruDirF& o, const vmmt_gru_dir_fwd& i) {
   o.h_prev = i.h_prev; o.ld_hprev = i.ld_hprev; o.w_hh = i.w_hh; o.ld_w = i.ld_w; o.gx = (const float*)i.gx; o.ld_gx = i.ld_gx;
   o.gx2 = (const float*)i.gx2; o.ld_gx2 = i.ld_gx2; o.b_hn = (const float*)i.b_hn; o.saved = i.saved; o.ld_saved = i.ld_saved;
@@ -469,7 +459,7 @@ extern "C" int vmmt_gru_step_fwd(int dtype, int ndir, const vmmt_gru_dir_fwd* di
   hipStream_t st = (hipStream_t)stream;
   if (dtype == VMMT_BF16 && H % 32 == 0) {
     bool ok = true;
-    for (int k = 0; k < ndir; ++k) ok = ok && gru_al16(dirs[k].h_prev, dirs[k].ld_hprev) && gru_al16(dirs[k].w_hh, dirs[k].ld_w);
+    for (int k = 0; k < ndir; ++k) ok = ok && al16(dirs[k].h_prev, dirs[k].ld_hprev) && al16(dirs[k].w_hh, dirs[k].ld_w);
     if (ok) {
       switch (gru_chunk(H)) {
         case 512: return gru_launch_fwd_fast<512>(a, ndir, st);
@@ -510,7 +500,7 @@ extern "C" int vmmt_gru_step_bwd(int dtype, int ndir, const vmmt_gru_dir_bwd* di
   if (dtype == VMMT_BF16 && H % 32 == 0) {
     bool ok = true;
     for (int k = 0; k < ndir; ++k)
-      ok = ok && (!dirs[k].dgh_next || (gru_al16(dirs[k].dgh_next, dirs[k].ld_dgn) && gru_al16(dirs[k].w_hh_t, dirs[k].ld_wt)));
+      ok = ok && (!dirs[k].dgh_next || (al16(dirs[k].dgh_next, dirs[k].ld_dgn) && al16(dirs[k].w_hh_t, dirs[k].ld_wt)));
     if (ok) {
       switch (gru_chunk(H)) {
         case 512: return gru_launch_bwd_fast<512>(a, ndir, st);
@@ -535,20 +525,10 @@ extern "C" int vmmt_gru_step_bwd(int dtype, int ndir, const vmmt_gru_dir_bwd* di
 // a whole recurrence in one host call: nsteps launches, step i described by dirs[i*ndir .. i*ndir+ndir)
 extern "C" int vmmt_gru_chain_fwd(int dtype, int ndir, int nsteps, const vmmt_gru_dir_fwd* dirs, const int64_t* lens, int B,
                                   int H, void* stream) {
-  if (nsteps < 0 || !dirs) return VMMT_EINVAL;
-  for (int i = 0; i < nsteps; ++i) {
-    int rc = vmmt_gru_step_fwd(dtype, ndir, dirs + (long)i * ndir, lens, B, H, stream);
-    if (rc != VMMT_OK) return rc;
-  }
-  return VMMT_OK;
+  return vmmt::chain_steps(ndir, nsteps, dirs, [&](const vmmt_gru_dir_fwd* d) { return vmmt_gru_step_fwd(dtype, ndir, d, lens, B, H, stream); });
 }
 
 extern "C" int vmmt_gru_chain_bwd(int dtype, int ndir, int nsteps, const vmmt_gru_dir_bwd* dirs, const int64_t* lens, int B,
                                   int H, int mode, void* stream) {
-  if (nsteps < 0 || !dirs) return VMMT_EINVAL;
-  for (int i = 0; i < nsteps; ++i) {
-    int rc = vmmt_gru_step_bwd(dtype, ndir, dirs + (long)i * ndir, lens, B, H, mode, stream);
-    if (rc != VMMT_OK) return rc;
-  }
-  return VMMT_OK;
+  return vmmt::chain_steps(ndir, nsteps, dirs, [&](const vmmt_gru_dir_bwd* d) { return vmmt_gru_step_bwd(dtype, ndir, d, lens, B, H, mode, stream); });
 }

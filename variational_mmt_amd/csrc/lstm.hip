@@ -203,14 +203,6 @@ __device__ unsigned long long vmmt_probe_ts[64 * 16];
 #define VMMT_TS(i) do {} while (0)
 #endif
 
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void glb_cvoid_t;
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void dma16(const char* src, char* dst_uniform) {
-  __builtin_amdgcn_global_load_lds((glb_cvoid_t*)src, (lds_void_t*)dst_uniform, 16, 0, 0);
-}
-
 // epilogue operands of the forward cell, fetched right behind the staging loads so that their latency hides behind them
 struct CellInF { float gx[4]; float cp; long long len; };
 __device__ __forceinline__ CellInF cell_fwd_load(const StepDirF& d, const long long* lens, int b, int u, int H, int B) {
@@ -469,8 +461,6 @@ static int launch_bwd_fast(const StepArgsB& a, int ndir, hipStream_t st) {
   return check_launch();
 }
 
-static bool al16(const void* p, long ld_elems) { return (((uintptr_t)p) & 15) == 0 && (ld_elems * 2) % 16 == 0; }
-
 static void fill_f(StepDirF& o, const vmmt_lstm_dir_fwd& i) {
   o.h_prev = i.h_prev; o.ld_hprev = i.ld_hprev; o.c_prev = (const float*)i.c_prev; o.ld_cprev = i.ld_cprev;
   o.w_hh = i.w_hh; o.ld_w = i.ld_w; o.gx = (const float*)i.gx; o.ld_gx = i.ld_gx; o.gx2 = (const float*)i.gx2;
@@ -571,20 +561,10 @@ extern "C" int vmmt_lstm_step_bwd(int dtype, int ndir, const vmmt_lstm_dir_bwd* 
 // training step at B = 256, which made the Python/ctypes host side the bottleneck).
 extern "C" int vmmt_lstm_chain_fwd(int dtype, int ndir, int nsteps, const vmmt_lstm_dir_fwd* dirs, const int64_t* lens, int B,
                                    int H, void* stream) {
-  if (nsteps < 0 || !dirs) return VMMT_EINVAL;
-  for (int i = 0; i < nsteps; ++i) {
-    int rc = vmmt_lstm_step_fwd(dtype, ndir, dirs + (long)i * ndir, lens, B, H, stream);
-    if (rc != VMMT_OK) return rc;
-  }
-  return VMMT_OK;
+  return vmmt::chain_steps(ndir, nsteps, dirs, [&](const vmmt_lstm_dir_fwd* d) { return vmmt_lstm_step_fwd(dtype, ndir, d, lens, B, H, stream); });
 }
 
 extern "C" int vmmt_lstm_chain_bwd(int dtype, int ndir, int nsteps, const vmmt_lstm_dir_bwd* dirs, const int64_t* lens, int B,
                                    int H, int mode, void* stream) {
-  if (nsteps < 0 || !dirs) return VMMT_EINVAL;
-  for (int i = 0; i < nsteps; ++i) {
-    int rc = vmmt_lstm_step_bwd(dtype, ndir, dirs + (long)i * ndir, lens, B, H, mode, stream);
-    if (rc != VMMT_OK) return rc;
-  }
-  return VMMT_OK;
+  return vmmt::chain_steps(ndir, nsteps, dirs, [&](const vmmt_lstm_dir_bwd* d) { return vmmt_lstm_step_bwd(dtype, ndir, d, lens, B, H, mode, stream); });
 }

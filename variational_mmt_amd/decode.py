@@ -18,14 +18,14 @@ import ctypes as C
 import torch
 
 from . import _lib as L
-from .engine import Buf, KPAD, PAD, _ru
+from .engine import Buf, KPAD, PAD, _ru, recurrence
 
 
 class _Stepper(object):
     """Buffers and launches of one decoder position for R rows (R = B for arg-max decoding, K*B for beam search).
     State is double-buffered: a position reads set 0 (h of the lower layers, c, right half of cat[0]) and writes set 1."""
 
-    def __init__(self, eng, R, S, ctx, ctx_ld, src_len, zx, zx_ld):
+    def __init__(self, eng, R, S, ctx, ctx_ld, src_len, zx):
         self.eng, self.R, self.S = eng, R, S
         d, dev, T, f32 = eng.d, eng.dev, eng.T, torch.float32
         H, E, Lyr = d.hid, d.emb, d.layers
@@ -40,8 +40,15 @@ class _Stepper(object):
         self.cat = [nb(R, 2 * Hp), nb(R, 2 * Hp)]
         self.Q, self.AH = nb(R, H), nb(R, H)
         self.probs = torch.zeros(R * S, dtype=f32, device=dev)
-        self.ctx, self.ctx_ld, self.src_len, self.zx, self.zx_ld = ctx, ctx_ld, src_len, zx, zx_ld
+        self.ctx, self.ctx_ld, self.src_len = ctx, ctx_ld, src_len
         self.UH = nb(S * R, H) if d.attn == "mlp" else None      # W_c Hs of the mlp attention: per batch, not per position
+        # every layer's time step as a recurrence of ONE step from a given state (set 0), written to set 1; layer 0 adds `zx` (a buffer:
+        # z W_z^T + b_ih + b_hh -- the GRU: b_hh's r and z parts --, constant over the sentence)
+        self.cell, self.sites = recurrence.CELLS[d.rnn], []
+        for l in range(Lyr):
+            (hp, hcol), (ho, ocol), (c0, c1) = self.h_buf(l, 0), self.h_buf(l, 1), (self.c[l] if self.c else (None, None))
+            self.sites.append(recurrence.Site(1, 1, R, Hp, d.gates, ho, self.gates, ocol=ocol, c=c1, h0=hp, h0col=hcol, c0=c0, gx=self.gx[l],
+                                              gx2=zx if l == 0 else None, w_hh=[eng.sh["dec_whh_l%d" % l]], b_hn=[eng.sh.get("dec_bhn_l%d" % l)]))
 
     def prepare(self):
         """what depends on the batch's source memory alone, once the decoder state is built: UH = Hs W_c^T (GlobalAttention.py:122-123)"""
@@ -76,33 +83,8 @@ class _Stepper(object):
                 wi, bs = e.sh["dec_wih_l%d" % l], e.sh["dec_b_l%d" % l]
                 self.gemm(L.GEMM_NT, x.p(0, xoff), x.ld, wi.p(), wi.ld, gx.p(), gx.ld, R, d.gates * Hp, xcols, addend=bs.p(), ld_add=bs.ld,
                           add_rows=1, out_f32=1)
-            hp, ho = self.h_buf(l, 0), self.h_buf(l, 1)
-            whh = e.sh["dec_whh_l%d" % l]
-            if self.gru:
-                arr = (L.GruDirFwd * 2)()
-                a = arr[0]
-                a.h_prev, a.ld_hprev, a.w_hh, a.ld_w, a.gx, a.ld_gx = hp[0].p(0, hp[1]), hp[0].ld, whh.p(), whh.ld, gx.p(), gx.ld
-                if l == 0:
-                    a.gx2, a.ld_gx2 = self.zx, self.zx_ld        # z W_z^T + b_ih + b_hh's r and z parts
-                a.b_hn, a.saved, a.ld_saved = e.sh["dec_bhn_l%d" % l].p(), self.gates.p(), self.gates.ld
-                a.h_out, a.ld_h, a.t, a.capture = ho[0].p(0, ho[1]), ho[0].ld, t, 0
-                L.check(lib.vmmt_gru_step_fwd(dt, 1, arr, None, R, Hp, st), "vmmt_gru_step_fwd")
-                x, xoff, xcols = ho[0], ho[1], H
-                continue
-            arr = (L.LstmDirFwd * 2)()
-            a = arr[0]
-            a.h_prev, a.ld_hprev = hp[0].p(0, hp[1]), hp[0].ld
-            a.c_prev, a.ld_cprev = self.c[l][0].p(), self.c[l][0].ld
-            a.w_hh, a.ld_w = whh.p(), whh.ld
-            a.gx, a.ld_gx = gx.p(), gx.ld
-            if l == 0:
-                a.gx2, a.ld_gx2 = self.zx, self.zx_ld            # z W_z^T + b_ih + b_hh, constant over the sentence
-            a.gates, a.ld_gates = self.gates.p(), self.gates.ld
-            a.c_out, a.ld_c = self.c[l][1].p(), self.c[l][1].ld
-            a.h_out, a.ld_h = ho[0].p(0, ho[1]), ho[0].ld
-            a.t, a.capture = t, 0
-            L.check(lib.vmmt_lstm_step_fwd(dt, 1, arr, None, R, Hp, st), "vmmt_lstm_step_fwd")
-            x, xoff, xcols = ho[0], ho[1], H
+            recurrence.step_forward(lib, self.cell, dt, self.sites[l], t, st)
+            (x, xoff), xcols = self.h_buf(l, 1), H
         cat = self.cat[1]
         wa, wo = e.sh["wa"], e.sh["wo"]
         if d.attn == "mlp":
@@ -182,7 +164,7 @@ def greedy_decode(eng, src, src_len, max_len=50, bos=2, eos=None, check_every=16
         b.update(pm=torch.zeros(n, dtype=f32, device=dev), ps=torch.zeros(n, dtype=f32, device=dev),
                  pi=torch.zeros(n, dtype=torch.int32, device=dev), tl=torch.zeros(B, dtype=f32, device=dev),
                  nll=torch.zeros(B, dtype=f32, device=dev), stats=torch.zeros(L.STAT_COUNT, dtype=f32, device=dev))
-        b["stepper"] = _Stepper(eng, B, S, b["ctx"].p(), b["ctx"].ld, b["src_len"], b["zx"].p(), b["zx"].ld)
+        b["stepper"] = _Stepper(eng, B, S, b["ctx"].p(), b["ctx"].ld, b["src_len"], b["zx"])
         eng.ws[key] = b
     sp, tok = b["stepper"], b["tok"]
     wg = eng.sh["wg"]
@@ -248,7 +230,7 @@ def beam_decode(eng, src, src_len, beam_size, max_len=100, min_length=0, bos=2, 
                  st_score=torch.zeros(B, K, dtype=f32, device=dev), st_prev=torch.zeros(B, K, dtype=torch.int32, device=dev),
                  st_next=torch.zeros(B, K, dtype=i64, device=dev), counter=torch.zeros(1, dtype=torch.int32, device=dev),
                  adv_ws=torch.zeros(int(lib.vmmt_beam_advance_ws_bytes(B, K, V)) // 4, dtype=f32, device=dev))
-        b["stepper"] = _Stepper(eng, R, S, b["ctx"].p(), b["ctx"].ld, b["src_len"], b["zx"].p(), b["zx"].ld)
+        b["stepper"] = _Stepper(eng, R, S, b["ctx"].p(), b["ctx"].ld, b["src_len"], b["zx"])
         eng.ws[key] = b
     sp, tok = b["stepper"], b["tok"]
     wg, lg = eng.sh["wg"], b["logits"]

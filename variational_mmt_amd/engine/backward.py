@@ -6,6 +6,7 @@ from os import environ as _os_env
 import torch
 
 from .. import _lib as L
+from . import recurrence as R
 from .layout import Buf, KPAD, PAD, _ru  # noqa: F401
 
 
@@ -18,7 +19,7 @@ class BackwardPlan(object):
         B, S, Tp, M, MS = self.B, self.S, self.Tp, self.M, self.MS
         H, Hd, E, Z, D, V, Lyr, dirs = d.hid, d.hd, d.emb, d.z, d.img, d.vt, d.layers, d.dirs
         Hp, Hdp, G = d.hp, d.hdp, d.gates
-        gru = d.rnn == "GRU"
+        gru, cell = d.rnn == "GRU", R.CELLS[d.rnn]
         db_in_gemm = e.lstm_db_in_gemm and not gru      # (one column sum serves b_ih and b_hh of an LSTM only: the GRU's n parts differ)
         gmap_d, gmap_e = (Hp, H), (Hdp, Hd)       # padded gate blocks -> nn.LSTM's [4H] rows (vmmt_gemm_args.c_row_blk)
         dt = e.dt
@@ -384,47 +385,15 @@ class BackwardPlan(object):
             e._sid = MAIN
             last = l == Lyr - 1
             outb, ocol = (self.cat, Hp) if last else (self.dec_out[l], 0)
-            whhT = e.sh["dec_whhT_l%d" % l]
             dg = self.dec_dgates[l]
             dgr = self.dec_dgh[l] if gru else dg               # recurrent-side gate gradients (GRU: [dr, dz, dn r]; LSTM: the same matrix)
-            seq = ((L.GruDirBwd if gru else L.LstmDirBwd) * (Tp + 1))()                   # Tp cell-backward steps + the dh0 step
-            for i, t in enumerate(reversed(range(Tp)) if gru else ()):
-                a = seq[i]
-                if t < Tp - 1:
-                    a.dgh_next, a.ld_dgn = dgr.p((t + 1) * B), dgr.ld
-                a.w_hh_t, a.ld_wt = whhT.p(), whhT.ld
-                a.dh_above, a.ld_dha = dh_above.p(t * B), dh_above.ld
-                a.saved, a.ld_saved = self.dec_gates[l].p(t * B), self.dec_gates[l].ld
-                a.h_prev, a.ld_hp = (outb.p((t - 1) * B, ocol), outb.ld) if t > 0 else (self.hn[l].p(), self.hn[l].ld)
-                a.dh_carry, a.ld_dhc = self.dec_dcc[l].p(), self.dec_dcc[l].ld       # the f32 direct path dh z, in the LSTM's dc buffer
-                a.dgx_out, a.ld_dgx, a.dgh_out, a.ld_dgh = dg.p(t * B), dg.ld, dgr.p(t * B), dgr.ld
-                a.t, a.inject = t, 0
-            for i, t in enumerate(() if gru else reversed(range(Tp))):
-                a = seq[i]
-                if t < Tp - 1:
-                    a.dgates_next, a.ld_dgn = dg.p((t + 1) * B), dg.ld
-                a.w_hh_t, a.ld_wt = whhT.p(), whhT.ld
-                a.dh_above, a.ld_dha = dh_above.p(t * B), dh_above.ld
-                a.gates, a.ld_gates = self.dec_gates[l].p(t * B), self.dec_gates[l].ld
-                a.c_t, a.ld_ct = self.dec_c[l].p(t * B), self.dec_c[l].ld
-                if t > 0:
-                    a.c_prev, a.ld_cp = self.dec_c[l].p((t - 1) * B), self.dec_c[l].ld
-                else:
-                    a.c_prev, a.ld_cp = self.cn[l].p(), self.cn[l].ld
-                a.dc_carry, a.ld_dcc = self.dec_dcc[l].p(), self.dec_dcc[l].ld
-                a.dgates_out, a.ld_dgo = dg.p(t * B), dg.ld
-                a.t, a.inject = t, 0
-            a = seq[Tp]                                        # gradient of the initial hidden state: dgates_0 W_hh (mode 1)
-            if gru:                                            # ... + the direct path left in the carry
-                a.dgh_next, a.ld_dgn = dgr.p(0), dgr.ld
-                a.dh_carry, a.ld_dhc = self.dec_dcc[l].p(), self.dec_dcc[l].ld
-            else:
-                a.dgates_next, a.ld_dgn = dg.p(0), dg.ld
-            a.w_hh_t, a.ld_wt = whhT.p(), whhT.ld
-            a.dh0_out, a.ld_dh0 = self.dec_dh0[l].p(), self.dec_dh0[l].ld
+            # Tp cell-backward steps + the gradient of the initial hidden state (dh0: dgates_0 W_hh, mode 1).  The carry is the LSTM's
+            # dc, the GRU's f32 direct path dh z
             # (conditional model: encoder_tgt's persistent backward is running by now; two persistent launches share a CU only if their
             #  registers fit one SIMD file and their LDS one CU -- 272 + 166 registers, 72 + 40 KiB here)
-            (e._gru_seq_bwd if gru else e._lstm_seq_bwd)(P, seq, 1, Tp, None, B, Hp, with_dh0=1)
+            R.emit_backward(e, P, cell, R.Site(
+                Tp, 1, B, Hp, G, outb, self.dec_gates[l], ocol=ocol, c=self.dec_c[l], h0=self.hn[l], c0=self.cn[l], dh_above=dh_above,
+                dgx=dg, dgh=dgr, carry=self.dec_dcc[l], w_hh_t=[e.sh["dec_whhT_l%d" % l]], dh0=self.dec_dh0[l]))
             e._record(P, "dec_dg%d" % l)
             if l > 0:       # gradient w.r.t. the layer input stays on the critical path
                 wi = e.sh["dec_wih_l%d" % l]
@@ -604,52 +573,14 @@ class BackwardPlan(object):
                 e._wait(P, "enc_top_dx")
             dg = self.enc_dgates[l]
             dgr = self.enc_dgh[l] if gru else dg
-            seq = ((L.GruDirBwd if gru else L.LstmDirBwd) * (S * dirs))()
-            for step in range(S if gru else 0):
-                for k in range(dirs):
-                    t = (S - 1 - step) if k == 0 else step
-                    tn = (t + 1) if k == 0 else (t - 1)
-                    tp = (t - 1) if k == 0 else (t + 1)        # forward predecessor (h_prev; none: the zero state)
-                    a = seq[step * dirs + k]
-                    whhT = e.sh["enc_whhT_l%d_d%d" % (l, k)]
-                    if step > 0:
-                        a.dgh_next, a.ld_dgn = dgr.p(tn * B, k * G * Hdp), dgr.ld
-                    a.w_hh_t, a.ld_wt = whhT.p(), whhT.ld
-                    a.dh_above, a.ld_dha = dh_above.p(t * B, k * Hdp), dh_above.ld
-                    a.saved, a.ld_saved = self.enc_gates[l].p(t * B, k * 4 * Hdp), self.enc_gates[l].ld
-                    if 0 <= tp < S:
-                        a.h_prev, a.ld_hp = self.enc_out[l].p(tp * B, k * Hdp), self.enc_out[l].ld
-                    a.dh_carry, a.ld_dhc = self.enc_dcc[l].p(0, k * Hdp), self.enc_dcc[l].ld
-                    a.dgx_out, a.ld_dgx = dg.p(t * B, k * G * Hdp), dg.ld
-                    a.dgh_out, a.ld_dgh = dgr.p(t * B, k * G * Hdp), dgr.ld
-                    a.dh_n, a.ld_dhn = self.dec_dh0[l].p(0, k * Hdp), self.dec_dh0[l].ld     # gradient of the encoder's final h (the decoder's h0)
-                    a.t, a.inject = t, (1 if k == 0 else 2)
-            for step in range(0 if gru else S):
-                for k in range(dirs):
-                    # backward visits the steps in the reverse of the forward order of that direction
-                    t = (S - 1 - step) if k == 0 else step
-                    tn = (t + 1) if k == 0 else (t - 1)        # step processed just before (its dgates feed the GEMM)
-                    tp = (t - 1) if k == 0 else (t + 1)        # forward predecessor (c_prev)
-                    a = seq[step * dirs + k]
-                    whhT = e.sh["enc_whhT_l%d_d%d" % (l, k)]
-                    if step > 0:
-                        a.dgates_next, a.ld_dgn = dg.p(tn * B, k * G * Hdp), dg.ld
-                    a.w_hh_t, a.ld_wt = whhT.p(), whhT.ld
-                    a.dh_above, a.ld_dha = dh_above.p(t * B, k * Hdp), dh_above.ld
-                    a.gates, a.ld_gates = self.enc_gates[l].p(t * B, k * 4 * Hdp), self.enc_gates[l].ld
-                    a.c_t, a.ld_ct = self.enc_c[l].p(t * B, k * Hdp), self.enc_c[l].ld
-                    if 0 <= tp < S:
-                        a.c_prev, a.ld_cp = self.enc_c[l].p(tp * B, k * Hdp), self.enc_c[l].ld
-                    a.dc_carry, a.ld_dcc = self.enc_dcc[l].p(0, k * Hdp), self.enc_dcc[l].ld
-                    a.dgates_out, a.ld_dgo = dg.p(t * B, k * G * Hdp), dg.ld
-                    a.dh_n, a.ld_dhn = self.dec_dh0[l].p(0, k * Hdp), self.dec_dh0[l].ld
-                    a.dc_n, a.ld_dcn = self.dec_dcc[l].p(0, k * Hdp), self.dec_dcc[l].ld
-                    a.t = t
-                    a.inject = 1 if k == 0 else 2
+            # from the zero state; injected: the gradients of the encoder's final h (and c), which are the decoder's dh0 (and its dc carry)
             # (the encoder's parameter gradients are the step's tail; cutting this recurrence into two launches so that the products of
             #  the first half of its steps run next to the second half was measured: 2.000 against 1.881 ms -- the relaunch has to wait
             #  for the product's workgroups to leave before all of its own are resident)
-            (e._gru_seq_bwd if gru else e._lstm_seq_bwd)(P, seq, dirs, S, self.src_len.data_ptr(), B, Hdp)
+            R.emit_backward(e, P, cell, R.Site(
+                S, dirs, B, Hdp, G, self.enc_out[l], self.enc_gates[l], c=self.enc_c[l], lens=self.src_len.data_ptr(), zero=self.hzero,
+                dh_above=dh_above, dgx=dg, dgh=dgr, carry=self.enc_dcc[l], w_hh_t=[e.sh["enc_whhT_l%d_d%d" % (l, k)] for k in range(dirs)],
+                dh_n=self.dec_dh0[l], dc_n=self.dec_dcc[l]))
             e._record(P, "enc_dg%d" % l)
             wih = e.sh["enc_wih_l%d" % l]
             if l > 0:

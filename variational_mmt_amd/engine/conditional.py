@@ -6,6 +6,7 @@ from os import environ as _os_env
 import torch
 
 from .. import _lib as L
+from . import recurrence as R
 from .layout import Buf, KPAD, PAD, _ru  # noqa: F401
 
 
@@ -71,27 +72,10 @@ class ConditionalPlans(object):
             wih, bsum = e.sh["enct_wih_l%d" % l], e.sh["enct_b_l%d" % l]
             e._gemm(P, L.GEMM_NT, x.p(), x.ld, wih.p(), wih.ld, self.enct_gx[l].p(), self.enct_gx[l].ld, MT, 8 * ht, xcols,
                     addend=bsum.p(), ld_add=bsum.ld, add_rows=1, out_f32=1)
-            arr = (L.LstmDirFwd * (2 * B))()                    # the whole recurrence is ONE host call (vmmt_lstm_chain_fwd)
-            for step in range(B):
-                for k in range(2):
-                    t = step if k == 0 else B - 1 - step           # "time" = sentence index (H5)
-                    tp = (t - 1) if k == 0 else (t + 1)
-                    first = step == 0
-                    whh = e.sh["enct_whh_l%d_d%d" % (l, k)]
-                    a = arr[2 * step + k]
-                    if first:
-                        a.h_prev, a.ld_hprev = self.enct_hzero.p(0, k * ht), self.enct_hzero.ld
-                    else:
-                        a.h_prev, a.ld_hprev = self.enct_out[l].p(tp * Tn, k * ht), self.enct_out[l].ld
-                        a.c_prev = self.enct_c[l].p(tp * Tn, k * ht)
-                    a.ld_cprev = self.enct_c[l].ld
-                    a.w_hh, a.ld_w = whh.p(), whh.ld
-                    a.gx, a.ld_gx = self.enct_gx[l].p(t * Tn, k * 4 * ht), self.enct_gx[l].ld
-                    a.gates, a.ld_gates = self.enct_gates[l].p(t * Tn, k * 4 * ht), self.enct_gates[l].ld
-                    a.c_out, a.ld_c = self.enct_c[l].p(t * Tn, k * ht), self.enct_c[l].ld
-                    a.h_out, a.ld_h = self.enct_out[l].p(t * Tn, k * ht), self.enct_out[l].ld
-                    a.t, a.capture = t, 0
-            e._lstm_seq_fwd(P, arr, 2, B, None, Tn, ht)
+            # B steps of Tn rows: "time" = sentence index (H5); from the zero state, no final-state capture
+            R.emit_forward(e, P, R.LSTM, R.Site(
+                B, 2, Tn, ht, 4, self.enct_out[l], self.enct_gates[l], c=self.enct_c[l], zero=self.enct_hzero, gx=self.enct_gx[l],
+                w_hh=[e.sh["enct_whh_l%d_d%d" % (l, k)] for k in range(2)]))
             x, xcols = self.enct_out[l], 2 * ht
             if l < Lyr - 1 and drop:
                 e._call(P, lib.vmmt_mul, dt, self.enct_out[l].p(), self.enct_out[l].ld, self.enct_mask[l].p(), self.enct_mask[l].ld,
@@ -178,26 +162,9 @@ class ConditionalPlans(object):
         for l in reversed(range(Lyr)):
             dg = self.enct_dgates[l]
             e._zero(P, [self.enct_dcc[l].t])
-            arr = (L.LstmDirBwd * (2 * B))()
-            for step in range(B):
-                for k in range(2):
-                    t = (B - 1 - step) if k == 0 else step
-                    tn = (t + 1) if k == 0 else (t - 1)
-                    tp = (t - 1) if k == 0 else (t + 1)
-                    a = arr[2 * step + k]
-                    whhT = e.sh["enct_whhT_l%d_d%d" % (l, k)]
-                    if step > 0:
-                        a.dgates_next, a.ld_dgn = dg.p(tn * Tn, k * 4 * ht), dg.ld
-                    a.w_hh_t, a.ld_wt = whhT.p(), whhT.ld
-                    a.dh_above, a.ld_dha = dh_above.p(t * Tn, k * ht), dh_above.ld
-                    a.gates, a.ld_gates = self.enct_gates[l].p(t * Tn, k * 4 * ht), self.enct_gates[l].ld
-                    a.c_t, a.ld_ct = self.enct_c[l].p(t * Tn, k * ht), self.enct_c[l].ld
-                    if 0 <= tp < B:
-                        a.c_prev, a.ld_cp = self.enct_c[l].p(tp * Tn, k * ht), self.enct_c[l].ld
-                    a.dc_carry, a.ld_dcc = self.enct_dcc[l].p(0, k * ht), self.enct_dcc[l].ld
-                    a.dgates_out, a.ld_dgo = dg.p(t * Tn, k * 4 * ht), dg.ld
-                    a.t, a.inject = t, 0
-            e._lstm_seq_bwd(P, arr, 2, B, None, Tn, ht)
+            R.emit_backward(e, P, R.LSTM, R.Site(
+                B, 2, Tn, ht, 4, self.enct_out[l], self.enct_gates[l], c=self.enct_c[l], zero=self.enct_hzero, dh_above=dh_above,
+                dgx=dg, dgh=dg, carry=self.enct_dcc[l], w_hh_t=[e.sh["enct_whhT_l%d_d%d" % (l, k)] for k in range(2)]))
             wih = e.sh["enct_wih_l%d" % l]
             if l > 0:
                 e._gemm(P, L.GEMM_NN, dg.p(), dg.ld, wih.p(), wih.ld, self.enct_dx[l - 1].p(), self.enct_dx[l - 1].ld, MT, 2 * ht, 8 * ht)

@@ -7,6 +7,7 @@ from os import environ as _os_env
 import torch
 
 from .. import _lib as L
+from . import recurrence as R
 from .backward import BackwardPlan
 from .conditional import ConditionalPlans
 from .layout import Buf, KPAD, PAD, _ru  # noqa: F401
@@ -181,7 +182,7 @@ class Workspace(BackwardPlan, ConditionalPlans):
         e, d, lib = self.e, self.e.d, self.e.lib
         B, S, Tp, M, MS = self.B, self.S, self.Tp, self.M, self.MS
         H, Hd, E, Z, D, V, Lyr, dirs = d.hid, d.hd, d.emb, d.z, d.img, d.vt, d.layers, d.dirs
-        Hp, Hdp, G = d.hp, d.hdp, d.gates
+        Hp, Hdp, G, cell = d.hp, d.hdp, d.gates, R.CELLS[d.rnn]
         dt = e.dt
         P = []
         drop = training and d.dropout > 0
@@ -331,46 +332,13 @@ class Workspace(BackwardPlan, ConditionalPlans):
             else:
                 e._gemm(P, L.GEMM_NT, x.p(), x.ld, wih.p(), wih.ld, self.enc_gx[l].p(), self.enc_gx[l].ld, MS, dirs * G * Hdp,
                         xcols, addend=bsum.p(), ld_add=bsum.ld, add_rows=1, out_f32=1)
-            gru = d.rnn == "GRU"
-            seq = ((L.GruDirFwd if gru else L.LstmDirFwd) * (S * dirs))()                 # the whole recurrence: step-major, then direction
             if not hasattr(self, "hzero"):
                 self.hzero = Buf(B, H, e.T, e.dev)              # first step: h_prev reads zeros
-            for step in range(S if gru else 0):
-                for k in range(dirs):                            # GRU: no cell state; r, z, n, hn saved in the LSTM's gate buffer
-                    t = step if k == 0 else S - 1 - step
-                    tp = (t - 1) if k == 0 else (t + 1)
-                    whh, a = e.sh["enc_whh_l%d_d%d" % (l, k)], seq[step * dirs + k]
-                    a.h_prev, a.ld_hprev = (self.hzero.p(0, k * Hdp), self.hzero.ld) if step == 0 else (self.enc_out[l].p(tp * B, k * Hdp), self.enc_out[l].ld)
-                    a.w_hh, a.ld_w = whh.p(), whh.ld
-                    a.gx, a.ld_gx = self.enc_gx[l].p(t * B, k * G * Hdp), self.enc_gx[l].ld
-                    a.b_hn = e.sh["enc_bhn_l%d_d%d" % (l, k)].p()
-                    a.saved, a.ld_saved = self.enc_gates[l].p(t * B, k * 4 * Hdp), self.enc_gates[l].ld
-                    a.h_out, a.ld_h = self.enc_out[l].p(t * B, k * Hdp), self.enc_out[l].ld
-                    a.h_n, a.ld_hn = self.hn[l].p(0, k * Hdp), self.hn[l].ld
-                    a.t, a.capture = t, (1 if k == 0 else 2)
-            for step in range(0 if gru else S):
-                for k in range(dirs):
-                    t = step if k == 0 else S - 1 - step
-                    tp = (t - 1) if k == 0 else (t + 1)
-                    first = step == 0
-                    whh = e.sh["enc_whh_l%d_d%d" % (l, k)]
-                    a = seq[step * dirs + k]
-                    a.h_prev = self.enc_out[l].p(tp * B, k * Hdp) if not first else self.enc_out[l].p(t * B, k * Hdp)
-                    a.ld_hprev = self.enc_out[l].ld
-                    a.c_prev = None if first else self.enc_c[l].p(tp * B, k * Hdp)
-                    a.ld_cprev = self.enc_c[l].ld
-                    a.w_hh, a.ld_w = whh.p(), whh.ld
-                    a.gx, a.ld_gx = self.enc_gx[l].p(t * B, k * G * Hdp), self.enc_gx[l].ld
-                    a.gates, a.ld_gates = self.enc_gates[l].p(t * B, k * 4 * Hdp), self.enc_gates[l].ld
-                    a.c_out, a.ld_c = self.enc_c[l].p(t * B, k * Hdp), self.enc_c[l].ld
-                    a.h_out, a.ld_h = self.enc_out[l].p(t * B, k * Hdp), self.enc_out[l].ld
-                    a.h_n, a.ld_hn = self.hn[l].p(0, k * Hdp), self.hn[l].ld
-                    a.c_n, a.ld_cn = self.cn[l].p(0, k * Hdp), self.cn[l].ld
-                    a.t = t
-                    a.capture = 1 if k == 0 else 2
-                    if first:
-                        a.h_prev, a.ld_hprev = self.hzero.p(0, k * Hdp), self.hzero.ld
-            (e._gru_seq_fwd if gru else e._lstm_seq_fwd)(P, seq, dirs, S, self.src_len.data_ptr(), B, Hdp)
+            # the whole recurrence from the zero state, final h (and c) captured for the decoder (descriptor rules: recurrence.py)
+            R.emit_forward(e, P, cell, R.Site(
+                S, dirs, B, Hdp, G, self.enc_out[l], self.enc_gates[l], c=self.enc_c[l], lens=self.src_len.data_ptr(), zero=self.hzero,
+                gx=self.enc_gx[l], w_hh=[e.sh["enc_whh_l%d_d%d" % (l, k)] for k in range(dirs)],
+                b_hn=[e.sh.get("enc_bhn_l%d_d%d" % (l, k)) for k in range(dirs)], hn=self.hn[l], cn=self.cn[l]))
             x, xcols = self.enc_out[l], H
             if l < Lyr - 1 and drop:
                 e._call(P, lib.vmmt_mul, dt, self.enc_out[l].p(), self.enc_out[l].ld, self.enc_mask[l].p(), self.enc_mask[l].ld,
@@ -460,36 +428,10 @@ class Workspace(BackwardPlan, ConditionalPlans):
                         addend=bs.p(), ld_add=bs.ld, add_rows=1, out_f32=1)
             last = l == Lyr - 1
             outb, ocol = (self.cat, Hp) if last else (self.dec_out[l], 0)
-            whh = e.sh["dec_whh_l%d" % l]
-            seq = ((L.GruDirFwd if gru else L.LstmDirFwd) * Tp)()
-            for t in range(Tp if gru else 0):                   # GRU: the initial state is the encoder's final h alone (Models.py:1167-1174)
-                a = seq[t]
-                a.h_prev, a.ld_hprev = (self.hn[l].p(), self.hn[l].ld) if t == 0 else (outb.p((t - 1) * B, ocol), outb.ld)
-                a.w_hh, a.ld_w = whh.p(), whh.ld
-                a.gx, a.ld_gx = self.dec_gx[l].p(t * B), self.dec_gx[l].ld
-                if l == 0:
-                    a.gx2, a.ld_gx2 = self.zx.p(), self.zx.ld
-                a.b_hn = e.sh["dec_bhn_l%d" % l].p()
-                a.saved, a.ld_saved = self.dec_gates[l].p(t * B), self.dec_gates[l].ld
-                a.h_out, a.ld_h = outb.p(t * B, ocol), outb.ld
-                a.h_n, a.t, a.capture = None, t, 0
-            for t in range(0 if gru else Tp):
-                a = seq[t]
-                if t == 0:
-                    a.h_prev, a.ld_hprev = self.hn[l].p(), self.hn[l].ld
-                    a.c_prev, a.ld_cprev = self.cn[l].p(), self.cn[l].ld
-                else:
-                    a.h_prev, a.ld_hprev = outb.p((t - 1) * B, ocol), outb.ld
-                    a.c_prev, a.ld_cprev = self.dec_c[l].p((t - 1) * B), self.dec_c[l].ld
-                a.w_hh, a.ld_w = whh.p(), whh.ld
-                a.gx, a.ld_gx = self.dec_gx[l].p(t * B), self.dec_gx[l].ld
-                if l == 0:
-                    a.gx2, a.ld_gx2 = self.zx.p(), self.zx.ld
-                a.gates, a.ld_gates = self.dec_gates[l].p(t * B), self.dec_gates[l].ld
-                a.c_out, a.ld_c = self.dec_c[l].p(t * B), self.dec_c[l].ld
-                a.h_out, a.ld_h = outb.p(t * B, ocol), outb.ld
-                a.h_n, a.c_n, a.t, a.capture = None, None, t, 0
-            (e._gru_seq_fwd if gru else e._lstm_seq_fwd)(P, seq, 1, Tp, None, B, Hp)
+            # from the encoder's final state (GRU: its h alone, Models.py:1167-1174); layer 0 adds z W_z^T + b per sentence
+            R.emit_forward(e, P, cell, R.Site(
+                Tp, 1, B, Hp, G, outb, self.dec_gates[l], ocol=ocol, c=self.dec_c[l], h0=self.hn[l], c0=self.cn[l], gx=self.dec_gx[l],
+                gx2=self.zx if l == 0 else None, w_hh=[e.sh["dec_whh_l%d" % l]], b_hn=[e.sh.get("dec_bhn_l%d" % l)]))
             if not last:
                 x, xcols = self.dec_out[l], H
                 if drop:
